@@ -22,7 +22,13 @@ each contracts ITS SHARE of the slices (``ctg_exec_run_share``: whole slice grou
 partial amplitudes are combined by ONE RCCL reduce on the executors' streams
 (``ctg_exec_reduce`` of the C ABI) inside the timed region -- weak scaling.
 
-Reports (rank 0): whole-node contracted FLOP/s, the dominant
+A plain run does what the headline needs and no more: set-up, ``--warmup`` slices, ``--steps``
+timed slices per GPU, the line (whole-node contracted FLOP/s, ``ms_per_step`` = milliseconds per
+timed slice).  ``--dump-outputs DIR`` writes what the timed slices computed -- the partial
+amplitude a caller receives, summed over the ranks -- as ``DIR/amplitude.npy`` (float32 [re, im]).
+Everything else is measured only with ``--full``.
+
+With ``--full`` it also reports (rank 0): the dominant
 kernel's roofline numbers measured live with HIP events, the numpy-oracle CPU
 baseline on this node's host cores (rank 0, every N; the launcher's
 OMP_NUM_THREADS=1 is lifted for it) and -- at N = 1 -- ``peak_rate_tree`` and the
@@ -870,9 +876,10 @@ def compact_record(out, full_path="bench_full.json"):
     sg = cfg.get("slice_groups")
     if sg:
         rec["config"]["slice_groups"] = _pick(sg, "slices_per_group", "shared_steps", "timed")
-    rec["roofline"] = _pick(roof, "bound", "kernel", "achieved", "peak", "unit", "frac", "avg_launch_ms",
-                            "launches_per_slice", "moved_bytes_per_launch", "algorithmic_bytes_per_launch",
-                            "flops_per_launch", "traffic", "share_of_slice_time")
+    if roof:   # (a plain run profiles no slice: no roofline)
+        rec["roofline"] = _pick(roof, "bound", "kernel", "achieved", "peak", "unit", "frac", "avg_launch_ms",
+                                "launches_per_slice", "moved_bytes_per_launch", "algorithmic_bytes_per_launch",
+                                "flops_per_launch", "traffic", "share_of_slice_time")
     if "matrix_side" in roof:
         rec["roofline"]["matrix_frac"] = roof["matrix_side"].get("frac")
     if "mixed_per_step" in roof:
@@ -957,6 +964,15 @@ def emit(out):
     print(line, flush=True)
 
 
+def dump_outputs(out_dir, result):
+    """What the timed region hands its caller: the partial amplitude of the timed slices (after the reduce: the
+    whole node's), as ``out_dir/amplitude.npy`` -- the result's shape + [re, im], float32 for complex64."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "amplitude.npy"), torch.view_as_real(result).cpu().numpy())
+
+
 def respawn(args):
     """No launcher in sight: start N ranks of this script through
     torch.distributed.run on the loopback address and pass its exit code on."""
@@ -978,11 +994,17 @@ def main():
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--tree", default=TREE)
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline as well: the dominant kernel's roofline "
+                         "(a profiled slice), the precision checks, the CPU-oracle baseline, the other trees and "
+                         "arithmetics, the C2/C3/C5 configs")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip every CPU-oracle leg (baseline, precision) and the extra workloads")
+                    help="(with --full) skip every CPU-oracle leg (baseline, precision) and the extra workloads")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip time_to_solution_tree and the C2/C3/C5 configs")
-    ap.add_argument("--dump-steps", default=None, help="write per-step timings JSON here")
+                    help="(with --full) skip time_to_solution_tree and the C2/C3/C5 configs")
+    ap.add_argument("--dump-steps", default=None, help="write per-step timings JSON here (profiles one slice)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed slices computed (the partial amplitude) as DIR/amplitude.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -1099,9 +1121,11 @@ def main():
              "share_units": int(plan.share_units(r, world)[0]), "slices_per_unit": int(plan.share_units(r, world)[1])}
             for r, v in enumerate(allr)
         ]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result)
 
-    extras = rank == 0 and world == 1 and not args.no_cpu_baseline
-    precision = precision_check(tree, arrays) if (rank == 0 and not args.no_cpu_baseline) else None
+    extras = rank == 0 and world == 1 and args.full and not args.no_cpu_baseline
+    precision = precision_check(tree, arrays) if (rank == 0 and args.full and not args.no_cpu_baseline) else None
     if precision is not None:
         # the quantity north_star gates: a sum of slices, without the numpy-relative clause
         psum = precision_sum_check(tree, arrays)
@@ -1110,7 +1134,7 @@ def main():
     # C3 at N > 1: every rank computes m10 amplitudes (of different bitstrings) on its own
     c3_amp = None
     # (CTG_BENCH_C3_AMPLITUDES=1: also at N = 1 under a launcher -- how the one-GPU lease tests this leg)
-    if (world > 1 or os.environ.get("CTG_BENCH_C3_AMPLITUDES")) and not args.headline_only:
+    if (world > 1 or os.environ.get("CTG_BENCH_C3_AMPLITUDES")) and args.full and not args.headline_only:
         try:
             mine3 = m10_amplitudes(dev)
         except Exception as e:  # noqa: BLE001  (an extra leg must not cost the headline line)
@@ -1141,7 +1165,7 @@ def main():
 
     # BASELINE config 3 as worded: the one 64-slice amplitude over the N ranks (strong scaling)
     c3_strong = None
-    if (world > 1 or os.environ.get("CTG_BENCH_C3_AMPLITUDES")) and not args.headline_only:
+    if (world > 1 or os.environ.get("CTG_BENCH_C3_AMPLITUDES")) and args.full and not args.headline_only:
         try:
             setup3 = m10_strong_setup(dev)
         except Exception as e:  # noqa: BLE001  (an extra leg must not cost the headline line)
@@ -1170,74 +1194,76 @@ def main():
     value = flops_slice * total_slices / dt
 
     if rank == 0:
-        rows = step_table(ex, plan)
-        dom_name, dom, by_name = dominant_kernel(rows, 8.0)
         arith_run = stem_arithmetic()
         bf3_run = arith_run if arith_run != "fp32" else False
-        dom_peak = step_peak_tflops(dom, bf3_run)
-        achieved_tf = dom["flops"] / (dom["ms"] * 1e-3) / 1e12
-        achieved_gbs = dom["moved"] / (dom["ms"] * 1e-3) / 1e9
-        # which roof binds the dominant kernel: the longer of flops / matrix peak and moved bytes / HBM peak
-        hbm_bound = dom["moved"] / (PEAK_HBM_GBS * 1e9) > dom["flops"] / (dom_peak * 1e12)
-        mf = [r for r in rows if r["kernel"] == "mfma"]
-        all_flops = sum(8.0 * r["macs"] for r in mf)
-        all_ms = sum(r["ms"] for r in mf)
-        slice_ms = sum(r["ms"] for r in rows)
-        bound_ms = mixed_roofline_ms(rows, 8.0, moved=True, bf16x3=bf3_run)
-        unfused_ms = mixed_roofline_ms(rows, 8.0, moved=False)
-        traffic, traffic_all = pmc_traffic_for(args.tree, dom_name)
         step_ms = dt * 1e3 / args.steps
-        roofline = {
-            "bound": "hbm" if hbm_bound else "mfma",
-            "kernel": dom_name,
-            "achieved": achieved_gbs if hbm_bound else achieved_tf,
-            "peak": PEAK_HBM_GBS if hbm_bound else dom_peak,
-            "unit": "GB/s" if hbm_bound else "TFLOP/s",
-            "frac": achieved_gbs / PEAK_HBM_GBS if hbm_bound else achieved_tf / dom_peak,
-            "bound_is": "the longer of flops / matrix peak and MOVED bytes / 8 TB/s for this kernel's launches; "
-                        "both sides follow",
-            # the matrix side: an fp16 x 2 pair is priced against fp16 peak / 3 products, a bf16 x 3 pair against
-            # bf16 peak / 6 (fp32-equivalent flops), an fp32 kernel against the fp32 matrix peak
-            "matrix_side": {"achieved_tflops": achieved_tf, "peak_tflops": dom_peak, "frac": achieved_tf / dom_peak,
-                            "pipe": ("fp16 MFMA, 3 products per fp32 product" if dom_peak == PEAK_FP16X2_TFLOPS
-                                     else "bf16 MFMA, 6 products per fp32 product" if dom_peak == PEAK_BF16X3_TFLOPS
-                                     else "fp32 MFMA")},
-            "hbm_side": {"achieved_gbs": achieved_gbs, "peak_gbs": PEAK_HBM_GBS, "frac": achieved_gbs / PEAK_HBM_GBS},
-            "launches_per_slice": dom["n"],
-            "avg_launch_ms": dom["ms"] / dom["n"],
-            "flops_per_launch": dom["flops"] / dom["n"],
-            # SURVEY 8(d) bytes of the launch's reference steps (a fused pair: both steps, incl. the
-            # intermediate it never writes) and the bytes the launch really moves; the HBM side of
-            # the kernel is priced on the latter, cross-checked by `traffic` (PMC)
-            "algorithmic_bytes_per_launch": dom["bytes"] / dom["n"],
-            "moved_bytes_per_launch": dom["moved"] / dom["n"],
-            "share_of_slice_time": dom["ms"] / max(slice_ms, 1e-9),
-            "traffic": traffic,
-            "traffic_source": "profiles/pmc_summary_%s.json (separate --pmc passes of this tree, committed; "
-                              "not measured in this run)" % os.path.splitext(os.path.basename(args.tree))[0],
-            "traffic_all_mfma_per_launch": traffic_all,
-            "all_mfma_kernels": {
-                "achieved_tflops": all_flops / (all_ms * 1e-3) / 1e12,
-                "launches_per_slice": len(mf),
-                "share_of_slice_time": all_ms / max(slice_ms, 1e-9),
-            },
-            "mixed_per_step": {
-                "definition": "THE BOUND: sum over steps of max(flops_i / matrix peak_i, MOVED bytes_i / 8 TB/s) -- a "
-                              "fused pair is priced on the bytes it moves (big operand in, result out) and against "
-                              "its own pipe (fp16 x 2: fp16 peak / 3; bf16 x 3: bf16 peak / 6); every other step "
-                              "against 157.3 TF",
-                "bound_ms": bound_ms,
-                "frac": bound_ms / step_ms,
-                "unfused_roofline_ms": unfused_ms,
-                "unfused_roofline_is": "the same sum with the SURVEY 8(d) bytes of the unfused reference steps: the "
-                                       "reference's execution model, which fused pairs may finish below -- reported, "
-                                       "not a bound of this executor",
-            },
-            "by_kernel_ms": {k: round(v["ms"], 3) for k, v in sorted(by_name.items(), key=lambda kv: -kv[1]["ms"])},
-        }
-        if args.dump_steps:
-            os.makedirs(os.path.dirname(os.path.abspath(args.dump_steps)), exist_ok=True)
-            json.dump(rows, open(args.dump_steps, "w"))
+        roofline = None
+        if args.full or args.dump_steps:   # (a slice profiled step by step: a run of its own)
+            rows = step_table(ex, plan)
+            dom_name, dom, by_name = dominant_kernel(rows, 8.0)
+            dom_peak = step_peak_tflops(dom, bf3_run)
+            achieved_tf = dom["flops"] / (dom["ms"] * 1e-3) / 1e12
+            achieved_gbs = dom["moved"] / (dom["ms"] * 1e-3) / 1e9
+            # which roof binds the dominant kernel: the longer of flops / matrix peak and moved bytes / HBM peak
+            hbm_bound = dom["moved"] / (PEAK_HBM_GBS * 1e9) > dom["flops"] / (dom_peak * 1e12)
+            mf = [r for r in rows if r["kernel"] == "mfma"]
+            all_flops = sum(8.0 * r["macs"] for r in mf)
+            all_ms = sum(r["ms"] for r in mf)
+            slice_ms = sum(r["ms"] for r in rows)
+            bound_ms = mixed_roofline_ms(rows, 8.0, moved=True, bf16x3=bf3_run)
+            unfused_ms = mixed_roofline_ms(rows, 8.0, moved=False)
+            traffic, traffic_all = pmc_traffic_for(args.tree, dom_name)
+            roofline = {
+                "bound": "hbm" if hbm_bound else "mfma",
+                "kernel": dom_name,
+                "achieved": achieved_gbs if hbm_bound else achieved_tf,
+                "peak": PEAK_HBM_GBS if hbm_bound else dom_peak,
+                "unit": "GB/s" if hbm_bound else "TFLOP/s",
+                "frac": achieved_gbs / PEAK_HBM_GBS if hbm_bound else achieved_tf / dom_peak,
+                "bound_is": "the longer of flops / matrix peak and MOVED bytes / 8 TB/s for this kernel's launches; "
+                            "both sides follow",
+                # the matrix side: an fp16 x 2 pair is priced against fp16 peak / 3 products, a bf16 x 3 pair against
+                # bf16 peak / 6 (fp32-equivalent flops), an fp32 kernel against the fp32 matrix peak
+                "matrix_side": {"achieved_tflops": achieved_tf, "peak_tflops": dom_peak, "frac": achieved_tf / dom_peak,
+                                "pipe": ("fp16 MFMA, 3 products per fp32 product" if dom_peak == PEAK_FP16X2_TFLOPS
+                                         else "bf16 MFMA, 6 products per fp32 product" if dom_peak == PEAK_BF16X3_TFLOPS
+                                         else "fp32 MFMA")},
+                "hbm_side": {"achieved_gbs": achieved_gbs, "peak_gbs": PEAK_HBM_GBS, "frac": achieved_gbs / PEAK_HBM_GBS},
+                "launches_per_slice": dom["n"],
+                "avg_launch_ms": dom["ms"] / dom["n"],
+                "flops_per_launch": dom["flops"] / dom["n"],
+                # SURVEY 8(d) bytes of the launch's reference steps (a fused pair: both steps, incl. the
+                # intermediate it never writes) and the bytes the launch really moves; the HBM side of
+                # the kernel is priced on the latter, cross-checked by `traffic` (PMC)
+                "algorithmic_bytes_per_launch": dom["bytes"] / dom["n"],
+                "moved_bytes_per_launch": dom["moved"] / dom["n"],
+                "share_of_slice_time": dom["ms"] / max(slice_ms, 1e-9),
+                "traffic": traffic,
+                "traffic_source": "profiles/pmc_summary_%s.json (separate --pmc passes of this tree, committed; "
+                                  "not measured in this run)" % os.path.splitext(os.path.basename(args.tree))[0],
+                "traffic_all_mfma_per_launch": traffic_all,
+                "all_mfma_kernels": {
+                    "achieved_tflops": all_flops / (all_ms * 1e-3) / 1e12,
+                    "launches_per_slice": len(mf),
+                    "share_of_slice_time": all_ms / max(slice_ms, 1e-9),
+                },
+                "mixed_per_step": {
+                    "definition": "THE BOUND: sum over steps of max(flops_i / matrix peak_i, MOVED bytes_i / 8 TB/s) -- a "
+                                  "fused pair is priced on the bytes it moves (big operand in, result out) and against "
+                                  "its own pipe (fp16 x 2: fp16 peak / 3; bf16 x 3: bf16 peak / 6); every other step "
+                                  "against 157.3 TF",
+                    "bound_ms": bound_ms,
+                    "frac": bound_ms / step_ms,
+                    "unfused_roofline_ms": unfused_ms,
+                    "unfused_roofline_is": "the same sum with the SURVEY 8(d) bytes of the unfused reference steps: the "
+                                           "reference's execution model, which fused pairs may finish below -- reported, "
+                                           "not a bound of this executor",
+                },
+                "by_kernel_ms": {k: round(v["ms"], 3) for k, v in sorted(by_name.items(), key=lambda kv: -kv[1]["ms"])},
+            }
+            if args.dump_steps:
+                os.makedirs(os.path.dirname(os.path.abspath(args.dump_steps)), exist_ok=True)
+                json.dump(rows, open(args.dump_steps, "w"))
         out = {
             "metric": "contracted FLOP/s (whole node), Sycamore n53 m20 sliced amplitude",
             "value": value,
@@ -1292,7 +1318,7 @@ def main():
             out["per_rank"] = per_rank
             out["distinct_gpus"] = len(set(devices))
         fn.close()
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(tree, arrays)
         if extras and not args.headline_only:
             if os.path.abspath(args.tree) != os.path.abspath(TTS_TREE) and os.path.exists(TTS_TREE):

@@ -387,7 +387,7 @@ def test_two_ranks_plain_c_driver_and_bench_line(tmp_path):
 
     def bench(n):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1",
-               "--headline-only", "--no-cpu-baseline"]
+               "--full", "--headline-only", "--no-cpu-baseline"]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-2000:]
         line = r.stdout.strip().splitlines()[-1]
@@ -405,7 +405,7 @@ def test_two_ranks_plain_c_driver_and_bench_line(tmp_path):
     # the amplitudes: rank 0 of the 2-rank run holds the sum of slices {2, 3} + {4, 5}... of its own
     # schedule; compare like with like -- 4 slices on one rank
     cmd1 = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-            "--headline-only", "--no-cpu-baseline"]
+            "--full", "--headline-only", "--no-cpu-baseline"]
     r1 = subprocess.run(cmd1, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r1.returncode == 0, r1.stderr[-2000:]
     full1 = json.load(open(os.path.join(ROOT, json.loads(r1.stdout.strip().splitlines()[-1])["full_record"])))

@@ -485,7 +485,7 @@ def test_bench_legs_of_the_multi_rank_run_under_a_one_rank_launcher():
     env = dict(os.environ, CTG_BENCH_C3_AMPLITUDES="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", "29517", os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = r.stdout.strip().splitlines()[-1]

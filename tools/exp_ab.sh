@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}; cd $R
 V=$1; shift
 TREES=${@:-sycamore_m20_native sycamore_m20_fused}
 run() {
-  env CTG_LIB=$2 timeout 300 python bench.py --headline-only --no-cpu-baseline --steps 8 --warmup 2 \
+  env CTG_LIB=$2 timeout 300 python bench.py --full --headline-only --no-cpu-baseline --steps 8 --warmup 2 \
       --tree tests/golden/trees/$3.json 2>/dev/null | tail -1 | \
       python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1 $3', round(d['ms_per_step'],2), 'ms/slice', round(d['tflops'],1), 'TFLOP/s')"
 }

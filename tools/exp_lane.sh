@@ -9,5 +9,5 @@ for mode in tables notables; do
 done 2>&1 | tee $O/ab.log
 unset CTG_NO_LANE_TABLES
 for t in sycamore_m20_w32_c512 sycamore_m20_native; do
-  timeout 300 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --tree tests/golden/trees/$t.json 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['config']['tree'], round(d['ms_per_step'],2), 'ms', round(d['tflops'],2), 'TF', {k:round(v,1) for k,v in list(d['roofline']['by_kernel_ms'].items())[:5]})"
+  timeout 300 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --tree tests/golden/trees/$t.json 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['config']['tree'], round(d['ms_per_step'],2), 'ms', round(d['tflops'],2), 'TF', {k:round(v,1) for k,v in list(d['roofline']['by_kernel_ms'].items())[:5]})"
 done 2>&1 | tee -a $O/ab.log

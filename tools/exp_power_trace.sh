@@ -3,7 +3,7 @@
 # in the driver's form -- the power-bound reading of DESIGN 4.2 (profiles/r5_power_trace.txt).
 R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/power; mkdir -p $O
 STEPS=${1:-20}
-python $R/bench.py --headline-only --no-cpu-baseline --steps $STEPS --warmup 5 > $O/bench.out 2> $O/bench.err &
+python $R/bench.py --full --headline-only --no-cpu-baseline --steps $STEPS --warmup 5 > $O/bench.out 2> $O/bench.err &
 BP=$!
 : > $O/smi.csv
 while kill -0 $BP 2>/dev/null; do

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/r4_trees; rm -rf $O; mkdir -p $O
 cd $R
 for t in "$@"; do
   n=$(basename $t .json)
-  timeout 300 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --headline-only --tree $R/$t --dump-steps $O/steps_$n.json > $O/$n.log 2>&1
+  timeout 300 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --headline-only --tree $R/$t --dump-steps $O/steps_$n.json > $O/$n.log 2>&1
   python - <<PY
 import json
 try:

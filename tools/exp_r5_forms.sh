@@ -8,7 +8,7 @@ TREE=${1:-sycamore_m20_native.json}
 for v in default xm r4form; do
   if [ $v = default ]; then unset CTG_LIB; else export CTG_LIB=$R/cotengra_amd/lib/exp/libctg_$v.so; fi
   [ $v != default ] && [ ! -f "$CTG_LIB" ] && continue
-  timeout 300 python $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --headline-only \
+  timeout 300 python $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --headline-only \
       --tree $R/tests/golden/trees/$TREE --dump-steps $O/steps_$v.json > $O/bench_$v.out 2> $O/bench_$v.err
   echo "$v: $(python -c "import json,sys; d=json.loads(open('$O/bench_$v.out').read().strip().splitlines()[-1]); print(d['ms_per_step'], d['roofline']['kernel'], d['roofline']['avg_launch_ms'], d['roofline']['frac'])")"
 done

@@ -7,7 +7,7 @@
 R=${GRAFT_REPO_ROOT:-$PWD}; cd $R
 run() {  # lib-tag tree env
   local lib=""; [ "$1" = r3 ] && lib=$R/cotengra_amd/lib/exp/libctg_r3stem.so
-  env CTG_LIB=$lib $3 timeout 300 python bench.py --headline-only --no-cpu-baseline --steps 8 --warmup 2 \
+  env CTG_LIB=$lib $3 timeout 300 python bench.py --full --headline-only --no-cpu-baseline --steps 8 --warmup 2 \
       --tree tests/golden/trees/$2.json 2>/dev/null | tail -1 | \
       python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1 $2 $3', round(d['ms_per_step'],2), 'ms/slice', round(d['tflops'],1), 'TFLOP/s')"
 }

@@ -2,7 +2,7 @@
 # SQ counters of the fused stem kernel on one slice of the headline tree: how busy the matrix
 # cores are, what the waves wait for (separate rocprofv3 --pmc passes, kernel trace only).
 R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/stem_sq; rm -rf $O; mkdir -p $O
-CMD="python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --headline-only --tree $R/tests/golden/trees/sycamore_m20_native.json"
+CMD="python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --headline-only --tree $R/tests/golden/trees/sycamore_m20_native.json"
 cd /tmp && export TMPDIR=/tmp
 i=0
 for set in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES" \

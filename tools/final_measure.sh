@@ -13,21 +13,21 @@ if [ "$1" != "notests" ]; then
   grep -E "passed|failed|error" $O/tests.log | tail -2
 fi
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
-timeout 900 python bench.py > $O/bench.log 2>&1
+timeout 900 python bench.py --full > $O/bench.log 2>&1
 tail -1 $O/bench.log > $O/bench_line.json
 cut -c1-400 $O/bench_line.json; echo
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats -d $O/trace -- python $R/bench.py > $O/trace.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats -d $O/trace -- python $R/bench.py --full > $O/trace.log 2>&1
 cd $R
 T=$(find $O/trace -name "*.db" | head -1)
 python tools/rocprof_summary.py $T $O/kernels > /dev/null 2>&1; head -14 $O/kernels_kernels.txt | cut -c1-190
 # the headline part alone: its per-kernel averages are what roofline.avg_launch_ms must agree with
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace_headline -- python $R/bench.py --headline-only --no-cpu-baseline --steps 4 --warmup 1 > $O/trace_headline.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace_headline -- python $R/bench.py --full --headline-only --no-cpu-baseline --steps 4 --warmup 1 > $O/trace_headline.log 2>&1
 cd $R
 python tools/rocprof_summary.py $(find $O/trace_headline -name "*.db" | head -1) $O/kernels_headline > /dev/null 2>&1; head -4 $O/kernels_headline_kernels.txt | cut -c1-190
 for tree in sycamore_m20_native sycamore_m20_w32_r4 sycamore_m20_w32_c512; do
-  CMD="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --tree $R/tests/golden/trees/$tree.json"
+  CMD="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --tree $R/tests/golden/trees/$tree.json"
   cd /tmp
   timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch_$tree -- $CMD > $O/pmc_fetch_$tree.log 2>&1
   timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_write_$tree -- $CMD > $O/pmc_write_$tree.log 2>&1
@@ -35,10 +35,10 @@ for tree in sycamore_m20_native sycamore_m20_w32_r4 sycamore_m20_w32_c512; do
   F=$(find $O/pmc_fetch_$tree -name "*.db" | head -1); W=$(find $O/pmc_write_$tree -name "*.db" | head -1)
   # (2 timed + 1 warm-up + 1 profiled slice = 4 slices in the run)
   python tools/pmc_traffic.py $F $W 4 $O/pmc_summary_$tree.json $tree.json | tail -8
-  timeout 600 python bench.py --steps 1 --warmup 1 --no-cpu-baseline --headline-only --tree tests/golden/trees/$tree.json --dump-steps $O/steps_$tree.json > /dev/null 2>&1
+  timeout 600 python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --headline-only --tree tests/golden/trees/$tree.json --dump-steps $O/steps_$tree.json > /dev/null 2>&1
   python tools/steps_report.py $O/steps_$tree.json 40 > $O/steps_$tree.txt 2>&1
   # the same slice with fp32 products in the fused pairs (CTG_STEM_BF16X3=0; the plan is priced for it and differs)
-  CTG_STEM_BF16X3=0 timeout 600 python bench.py --steps 1 --warmup 1 --no-cpu-baseline --headline-only --tree tests/golden/trees/$tree.json --dump-steps $O/steps_${tree}_fp32.json > /dev/null 2>&1
+  CTG_STEM_BF16X3=0 timeout 600 python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --headline-only --tree tests/golden/trees/$tree.json --dump-steps $O/steps_${tree}_fp32.json > /dev/null 2>&1
   python tools/steps_report.py $O/steps_${tree}_fp32.json 40 > $O/steps_${tree}_fp32.txt 2>&1
 done
 # the small configurations: kernel timeline of one contraction / slice batch, per-kernel

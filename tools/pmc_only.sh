@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/final
 mkdir -p $O
 for tree in sycamore_m20_w32_c512 sycamore_m20_native; do
-  CMD="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --headline-only --tree $R/tests/golden/trees/$tree.json"
+  CMD="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --headline-only --tree $R/tests/golden/trees/$tree.json"
   cd /tmp && export TMPDIR=/tmp
   rm -rf $O/pmc_fetch_$tree $O/pmc_write_$tree
   timeout ${1:-60} rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch_$tree -- $CMD > $O/pmc_fetch_$tree.log 2>&1
