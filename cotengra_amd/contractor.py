@@ -135,6 +135,83 @@ def _result_dtype(arrays):
     return dt
 
 
+def _device_copies(arrays, device, dtype):
+    """Contiguous tensors of ``dtype`` on ``device`` whose memory holds the values: a conjugate or
+    negative view keeps its bit through ``.to()`` / ``.contiguous()`` and would be read unconjugated."""
+    import torch
+
+    tdt = getattr(torch, dtype)
+    keep = []
+    for x in arrays:
+        if not _is_torch(x):
+            x = torch.as_tensor(np.asarray(x))
+        keep.append(x.detach().to(device=device, dtype=tdt).resolve_conj().resolve_neg().contiguous())
+    return keep
+
+
+def _host_copies(arrays):
+    return [x.detach().resolve_conj().resolve_neg().cpu().numpy() if _is_torch(x) else np.asarray(x)
+            for x in arrays]
+
+
+def _cast_like(g, x):
+    """Gradient ``g`` in the dtype of input ``x``: the real part for a real leaf of a complex contraction,
+    cast back for a promoted half-precision one."""
+    if _is_torch(g):
+        import torch
+
+        dt = x.dtype if _is_torch(x) else getattr(torch, np.asarray(x).dtype.name)
+        if g.is_complex() and not dt.is_complex:
+            g = g.real
+        return g.to(dt)
+    dt = np.dtype(str(x.dtype).replace("torch.", "")) if _is_torch(x) else np.asarray(x).dtype
+    if np.iscomplexobj(g) and dt.kind != "c":
+        g = g.real
+    return g.astype(dt)
+
+
+def _wants_grad(arrays):
+    """ROCm tensors, grad mode on and some input requiring grad: the autograd route."""
+    if not any(_is_torch(x) for x in arrays):
+        return False
+    import torch
+
+    return (torch.is_grad_enabled() and any(_is_torch(x) and x.is_cuda for x in arrays)
+            and any(_is_torch(x) and x.requires_grad for x in arrays))
+
+
+_ContractFunction = None
+
+
+def _autograd_function():
+    """The ``torch.autograd.Function`` of a whole-tree contraction (built on first use: torch is
+    optional).  The forward is the executor's own path -- the same bits as without autograd; the
+    backward is one VJP plan at the cotangent ``conj(grad_output)``, conjugated back (torch's
+    convention), for the inputs autograd asks for."""
+    global _ContractFunction
+    if _ContractFunction is not None:
+        return _ContractFunction
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class ContractFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fn, progbar, check_zero, *arrays):
+            ctx.fn = fn
+            ctx.arrays = [x.detach() if _is_torch(x) else x for x in arrays]
+            return fn._contract(ctx.arrays, progbar, check_zero, False)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_output):
+            wrt = [i for i, need in enumerate(ctx.needs_input_grad[3:]) if need]
+            grads = ctx.fn.vjp(*ctx.arrays, cotangent=grad_output.conj(), wrt=wrt)
+            return (None, None, None) + tuple(None if g is None else g.conj().resolve_conj() for g in grads)
+
+    _ContractFunction = ContractFunction
+    return ContractFunction
+
+
 class HipContractor:
     """Callable performing the contraction of ``tree`` on an MI355X.
 
@@ -228,15 +305,27 @@ class HipContractor:
             entry = self._plans[dtype] = (plan, runtime.DevicePlan(plan))
             return entry
 
-    def _get_exec(self, dtype, device, use_torch):
-        key = (dtype, device, use_torch)
+    def get_vjp_plan(self, dtype, wrt):
+        """The VJP plan of the leaves ``wrt`` (a sorted tuple) and its device plan."""
+        key = ("vjp", dtype, wrt)
+        try:
+            return self._plans[key]
+        except KeyError:
+            from .vjp import compile_vjp
+
+            plan = compile_vjp(self.tree, dtype, wrt=wrt, order=self.order)
+            entry = self._plans[key] = (plan, runtime.DevicePlan(plan))
+            return entry
+
+    def _get_exec(self, dtype, device, use_torch, wrt=None):
+        key = (dtype, device, use_torch) if wrt is None else (dtype, device, use_torch, "vjp", wrt)
         try:
             return self._execs[key]
         except KeyError:
             pass
-        plan, dplan = self.get_plan(dtype)
+        plan, dplan = self.get_plan(dtype) if wrt is None else self.get_vjp_plan(dtype, wrt)
         try:
-            st = self._new_exec(plan, dplan, dtype, device, use_torch)
+            st = self._new_exec(plan, dplan, dtype, device, use_torch, vjp=wrt is not None)
         except (MemoryError, RuntimeError) as exc:
             # Every cached contractor of a tree (``contract`` and ``contract_core``,
             # each dtype) keeps its own arena resident -- tens of GiB for a wide tree.
@@ -251,7 +340,7 @@ class HipContractor:
             freed = evict_expression_cache(keep=self) or freed
             if not freed:
                 raise
-            st = self._new_exec(plan, dplan, dtype, device, use_torch)
+            st = self._new_exec(plan, dplan, dtype, device, use_torch, vjp=wrt is not None)
         self._execs[key] = st
         return st
 
@@ -272,7 +361,7 @@ class HipContractor:
                 pass
         return freed
 
-    def _new_exec(self, plan, dplan, dtype, device, use_torch):
+    def _new_exec(self, plan, dplan, dtype, device, use_torch, vjp=False):
         st = {"plan": plan}
         if use_torch:
             import torch
@@ -293,6 +382,10 @@ class HipContractor:
             st["exec"].set_stem_arithmetic(self.stem_arith)
         elif self.stem_bf16x3 is not None:
             st["exec"].set_stem_arithmetic(self.stem_bf16x3)
+        elif vjp:
+            # (a VJP executor is uploaded with a new cotangent on every call; fp16 x 2 keeps per-tensor
+            # maxima across uploads, which could split a smaller cotangent under a stale scale)
+            st["exec"].set_stem_arithmetic("bf16x3")
         return st
 
     def setup(self, *arrays):
@@ -322,14 +415,7 @@ class HipContractor:
             if cur != st["stream"]:
                 st["exec"].set_stream(cur)
                 st["stream"] = cur
-            tdt = getattr(torch, dtype)
-            keep = []
-            for x in arrays:
-                if not _is_torch(x):
-                    x = torch.as_tensor(np.asarray(x))
-                keep.append(
-                    x.to(device=torch_in[0].device, dtype=tdt).contiguous()
-                )
+            keep = _device_copies(arrays, torch_in[0].device, dtype)
             st["exec"].upload_device(
                 [t.data_ptr() for t in keep], [t.numel() for t in keep]
             )
@@ -337,12 +423,71 @@ class HipContractor:
         else:
             device = self.device if self.device is not None else _current_device()
             st = self._get_exec(dtype, device, False)
-            host = [
-                x.detach().cpu().numpy() if _is_torch(x) else np.asarray(x)
-                for x in arrays
-            ]
-            st["exec"].upload_host(host)
+            st["exec"].upload_host(_host_copies(arrays))
         return st
+
+    # ---- gradients (cotengra_amd/vjp.py) ------------------------------------------------------------- #
+
+    def _vjp_state(self, arrays, cotangent, wrt):
+        """Upload ``arrays`` and ``cotangent`` to the VJP executor of ``wrt`` (cached in ``_execs`` with
+        the mask in the key, so that the out-of-memory eviction covers it) and return its state."""
+        tree = self.tree
+        if len(arrays) != tree.N:
+            raise ValueError(f"Expected {tree.N} arrays, got {len(arrays)}.")
+        for i, (x, s) in enumerate(zip(arrays, tree.get_shapes())):
+            if tuple(x.shape) != tuple(s):
+                raise ValueError(f"Array {i} has shape {tuple(x.shape)} but the tree expects {tuple(s)}.")
+        gshape = tuple(tree.gathered_shape())
+        if tuple(cotangent.shape) != gshape:
+            raise ValueError(f"cotangent has shape {tuple(cotangent.shape)}, the result {gshape}.")
+        everything = list(arrays) + [cotangent]
+        dtype = _result_dtype(everything)
+        torch_in = [x for x in everything if _is_torch(x) and x.is_cuda]
+        if torch_in:
+            import torch
+
+            device = torch_in[0].device.index or 0
+            st = self._get_exec(dtype, device, True, wrt=wrt)
+            cur = torch.cuda.current_stream(torch_in[0].device).cuda_stream
+            if cur != st["stream"]:
+                st["exec"].set_stream(cur)
+                st["stream"] = cur
+            keep = _device_copies(everything, torch_in[0].device, dtype)
+            st["exec"].upload_device([t.data_ptr() for t in keep], [t.numel() for t in keep])
+            st["keep"] = keep
+        else:
+            device = self.device if self.device is not None else _current_device()
+            st = self._get_exec(dtype, device, False, wrt=wrt)
+            st["exec"].upload_host(_host_copies(everything))
+        return st
+
+    def vjp(self, *arrays, cotangent, wrt=None):
+        """Vector-Jacobian product of the contraction: ``G_i = sum_o h[o] dO[o] / dx_i`` for ``h =
+        cotangent`` (the result's shape), summed over all slices -- JAX's convention, nothing conjugated.
+        Returns one gradient per leaf of ``wrt`` (default: all) and ``None`` for the others, each in its
+        input's dtype (the real part for a real leaf of a complex contraction).  numpy in, numpy out;
+        ROCm torch tensors in, tensors on that device out."""
+        if self.strip_exponent:
+            raise ValueError("vjp does not support strip_exponent.")
+        N = self.tree.N
+        wrt = tuple(range(N)) if wrt is None else tuple(sorted(set(int(i) for i in wrt)))
+        if not wrt:
+            return [None] * N
+        if wrt[0] < 0 or wrt[-1] >= N:
+            raise IndexError(f"wrt {wrt} outside the {N} leaves")
+        with self._lock:
+            st = self._vjp_state(arrays, cotangent, wrt)
+            ex = st["exec"]
+            ex.set_strip_exponent(False, False)
+            ex.zero_result()
+            self.run_share(ex, 0, 1, False)
+            flat = st["result"].clone() if "result" in st else ex.download_result()
+        plan = st["plan"]
+        out = [None] * N
+        for i in wrt:
+            off, n = plan.grad_offsets[i], plan.input_sizes[i]
+            out[i] = _cast_like(flat[off:off + n].reshape(tuple(arrays[i].shape)), arrays[i])
+        return out
 
     def _finish(self, st, strip_exponent, check_zero, index=None):
         """Fetch the result; with ``strip_exponent`` return ``(mantissa,
@@ -442,6 +587,11 @@ class HipContractor:
         kwargs.pop("implementation", None)
         if kwargs:
             raise TypeError(f"Unknown keyword arguments: {kwargs}.")
+        if not strip_exponent and _wants_grad(arrays):
+            return _autograd_function().apply(self, progbar, check_zero, *arrays)
+        return self._contract(arrays, progbar, check_zero, strip_exponent)
+
+    def _contract(self, arrays, progbar, check_zero, strip_exponent):
         with self._lock:
             st = self.setup(*arrays)
             ex = st["exec"]

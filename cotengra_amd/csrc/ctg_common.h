@@ -556,9 +556,24 @@ void stem2h_kernel_name(const StemArgs& p, char* buf, size_t n);
 
 hipError_t launch_single(int dtype, const StepArgs& p, hipStream_t stream);
 bool pair_bf16x3_on(const StepArgs& p);   // (ctg_pair_mfma.hip) do long tiled steps multiply with bf16 x 3 products right now?
-hipError_t launch_accum(int dtype, const StepArgs& p, const StripState* st, void* wide, const double* inscale, hipStream_t stream);
+// ``leaf``: the input whose own upload shift the coefficient leaves out (a gradient's accumulate, ABI 8), -1: none
+hipError_t launch_accum(int dtype, const StepArgs& p, const StripState* st, void* wide, const double* inscale, int leaf,
+                        hipStream_t stream);
+// (ABI 8) consecutive accumulate steps (the per-leaf gradients of a VJP plan) sharing one launch; item i owns
+// workgroups [block_begin, +n_blocks)
+struct AccumGroupItem {
+    StepArgs p;
+    void* wide;     // its double-precision running sum (null: the result is the sum)
+    int32_t leaf;   // as for launch_accum
+    uint32_t block_begin, n_blocks;
+};
+constexpr int64_t kAccumGroupMaxBlocks = 1 << 16;
+uint32_t accum_group_fill(const StepArgs& p, void* wide, int leaf, AccumGroupItem* it, uint32_t block_begin);   // -> n_blocks
+hipError_t launch_accum_group(int dtype, const AccumGroupItem* d_items, int n_items, uint32_t blocks, int nz,
+                              const double* inscale, hipStream_t stream);
 // (single-precision trees) inputs far from 1 are brought to [1, 2) by an exact power of two at upload; inscale[0] =
-// the product of the powers taken out, inscale[1] = its log10
+// the product of the powers taken out, inscale[1] = its log10; then as ints at inscale + 2: the sum of the shifts
+// and (ABI 8) each input's own shift
 hipError_t launch_prescale_inputs(int dtype, void* inputs, const int64_t* offs, const int64_t* sizes, int64_t n_inputs,
                                   int* shift_total, double* inscale, hipStream_t stream);
 // (float / complex64 results: the double-precision running sum next to the result -- ctg_kernels_valu.hip)

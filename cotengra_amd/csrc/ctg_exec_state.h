@@ -88,7 +88,8 @@ struct ctg_exec {
     int64_t scratch_total = 0;     // bytes of d_scratch (64 MiB x up to 8 for batching executors)
     // the launch list of one slice: steps that launch alone (cls < 0) and wave-front
     // groups -- n independent small steps of one kernel shape sharing a launch (cls 0:
-    // thread-per-output items, 1 + key: tiled fast-kernel items, starting at item0)
+    // thread-per-output items, 1 + key: tiled fast-kernel items, starting at item0; -2 LDS-resident subtrees;
+    // -3 consecutive accumulate steps)
     struct Issue {
         int64_t step;
         int cls;
@@ -105,6 +106,10 @@ struct ctg_exec {
     ctg::LdsCompDev* d_lds_comps = nullptr;
     char* d_lds_blob = nullptr;
     ctg::ValuGroupItem* d_group_items = nullptr;
+    // (ABI 8) runs of consecutive accumulate steps sharing one launch (cls -3 of Issue: accum_group_kernel), and
+    // which steps are members of such a run
+    ctg::AccumGroupItem* d_accum_items = nullptr;
+    std::vector<char> accum_member;
     ctg::FastGroupItem* d_fast_items = nullptr;
     std::vector<hipEvent_t> events;
     // slice graph: the launch sequence of one slice captured once and replayed,

@@ -435,16 +435,24 @@ __device__ __forceinline__ void narrow_to(double& d, double a) { d = a; }
 __device__ __forceinline__ void narrow_to(c64& d, c128 a) { d = c64{(float)a.re, (float)a.im}; }
 __device__ __forceinline__ void narrow_to(c128& d, c128 a) { d = a; }
 
+// (inscale: the power of two taken out of the input tensors at upload, prescale_inputs_kernel; a
+// strip_exponent run carries it in the exponent instead: strip_prepare_kernel.)  The coefficient of an
+// accumulate whose result operand names input ``leaf`` (a gradient, cotengra_amd/vjp.py) leaves that
+// input's own shift out: d result / d x_leaf carries every other input's power of two but not its own.
+__device__ __forceinline__ double accum_coef(const StripState* st, const double* inscale, int leaf) {
+    if (st) return st->coefm;
+    if (!inscale) return 1.0;
+    if (leaf < 0) return inscale[0];
+    const int* shifts = (const int*)(inscale + 2);   // [0] the total, [1 + i] input i's own
+    return ldexp(1.0, shifts[0] - shifts[1 + leaf]);
+}
+
+// rows row0, row0 + rstride, ... of one accumulate step
 template <typename T>
-__global__ __launch_bounds__(256) void accum_kernel(StepArgs p, const StripState* st, void* wide_, const double* inscale) {
+__device__ __forceinline__ void accum_rows(const StepArgs& p, double coef, bool scaled, typename wide_of<T>::type* wide,
+                                           int64_t row0, int64_t rstride) {
     typedef typename wide_of<T>::type W;
-    W* const wide = (W*)wide_;   // null: the result itself is the running sum
-    // (inscale: the power of two taken out of the input tensors at upload, prescale_inputs_kernel; a
-    // strip_exponent run carries it in the exponent instead: strip_prepare_kernel)
-    const double coef = st ? st->coefm : (inscale ? inscale[0] : 1.0);
-    const bool scaled = st != nullptr || coef != 1.0;
-    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < p.R;
-         row += (int64_t)gridDim.x * 256) {
+    for (int64_t row = row0; row < p.R; row += rstride) {
         int64_t hi, lo;
         split_row(p, row, hi, lo);
         const int64_t ra = p.rowA.hi[hi] + p.rowA.lo[lo], rc = p.rowC.hi[hi] + p.rowC.lo[lo];
@@ -484,15 +492,74 @@ __global__ __launch_bounds__(256) void accum_kernel(StepArgs p, const StripState
     }
 }
 
-hipError_t launch_accum(int dtype, const StepArgs& p, const StripState* st, void* wide, const double* inscale, hipStream_t stream) {
+template <typename T>
+__global__ __launch_bounds__(256) void accum_kernel(StepArgs p, const StripState* st, void* wide_, const double* inscale,
+                                                    int leaf) {
+    typedef typename wide_of<T>::type W;
+    // (wide null: the result itself is the running sum)
+    const double coef = accum_coef(st, inscale, leaf);
+    accum_rows<T>(p, coef, st != nullptr || coef != 1.0, (W*)wide_, (int64_t)blockIdx.x * 256 + threadIdx.x,
+                  (int64_t)gridDim.x * 256);
+}
+
+hipError_t launch_accum(int dtype, const StepArgs& p, const StripState* st, void* wide, const double* inscale, int leaf,
+                        hipStream_t stream) {
     int64_t blocks = (p.R + 255) / 256;
     if (blocks > (1 << 20)) blocks = 1 << 20;
     if (blocks < 1) blocks = 1;
     switch (dtype) {
-        case 0: hipLaunchKernelGGL(accum_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, stream, p, st, wide, inscale); break;
-        case 1: hipLaunchKernelGGL(accum_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, stream, p, st, nullptr, inscale); break;
-        case 2: hipLaunchKernelGGL(accum_kernel<c64>, dim3((unsigned)blocks), dim3(256), 0, stream, p, st, wide, inscale); break;
-        case 3: hipLaunchKernelGGL(accum_kernel<c128>, dim3((unsigned)blocks), dim3(256), 0, stream, p, st, nullptr, inscale); break;
+        case 0: hipLaunchKernelGGL(accum_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, stream, p, st, wide, inscale, leaf); break;
+        case 1: hipLaunchKernelGGL(accum_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, stream, p, st, nullptr, inscale, leaf); break;
+        case 2: hipLaunchKernelGGL(accum_kernel<c64>, dim3((unsigned)blocks), dim3(256), 0, stream, p, st, wide, inscale, leaf); break;
+        case 3: hipLaunchKernelGGL(accum_kernel<c128>, dim3((unsigned)blocks), dim3(256), 0, stream, p, st, nullptr, inscale, leaf); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// (ABI 8) A run of consecutive accumulate steps -- the per-leaf gradients that end a slice of a VJP plan --
+// as ONE launch: item i owns workgroups [block_begin, +n_blocks), dealt in proportion to its rows, and runs
+// accum_kernel's body on them.  The plan guarantees that the items write disjoint ranges (ctg_plan_create).
+// Each element still adds its slices in slice order: the same bits as one launch per step.
+template <typename T>
+__global__ __launch_bounds__(256) void accum_group_kernel(const AccumGroupItem* __restrict__ items, int n_items, int nz,
+                                                          const double* inscale) {
+    typedef typename wide_of<T>::type W;
+    const uint32_t b = blockIdx.x;
+    int lo = 0, hi = n_items - 1;   // the last item whose first workgroup is <= b
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (items[mid].block_begin <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    const AccumGroupItem& it = items[lo];
+    StepArgs p = it.p;
+    p.nz = nz;
+    const double coef = accum_coef(nullptr, inscale, it.leaf);
+    accum_rows<T>(p, coef, coef != 1.0, (W*)it.wide, (int64_t)(b - it.block_begin) * 256 + threadIdx.x,
+                  (int64_t)it.n_blocks * 256);
+}
+
+uint32_t accum_group_fill(const StepArgs& p, void* wide, int leaf, AccumGroupItem* it, uint32_t block_begin) {
+    int64_t blocks = (p.R + 255) / 256;
+    if (blocks > kAccumGroupMaxBlocks) blocks = kAccumGroupMaxBlocks;
+    if (blocks < 1) blocks = 1;
+    it->p = p;
+    it->wide = wide;
+    it->leaf = leaf;
+    it->block_begin = block_begin;
+    it->n_blocks = (uint32_t)blocks;
+    return (uint32_t)blocks;
+}
+
+hipError_t launch_accum_group(int dtype, const AccumGroupItem* d_items, int n_items, uint32_t blocks, int nz,
+                              const double* inscale, hipStream_t stream) {
+    if (n_items < 1 || blocks < 1) return hipSuccess;
+    switch (dtype) {
+        case 0: hipLaunchKernelGGL(accum_group_kernel<float>, dim3(blocks), dim3(256), 0, stream, d_items, n_items, nz, inscale); break;
+        case 1: hipLaunchKernelGGL(accum_group_kernel<double>, dim3(blocks), dim3(256), 0, stream, d_items, n_items, nz, inscale); break;
+        case 2: hipLaunchKernelGGL(accum_group_kernel<c64>, dim3(blocks), dim3(256), 0, stream, d_items, n_items, nz, inscale); break;
+        case 3: hipLaunchKernelGGL(accum_group_kernel<c128>, dim3(blocks), dim3(256), 0, stream, d_items, n_items, nz, inscale); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -545,6 +612,8 @@ __device__ __forceinline__ double abs_max_part(c64 a) { return fmax(fabs((double
 template <typename T>
 __global__ __launch_bounds__(256) void prescale_inputs_kernel(T* inputs, const int64_t* offs, const int64_t* sizes,
                                                               int* shift_total) {
+    // (shift_total[1 + i]: input i's own shift, which the gradient of input i leaves out: accum_coef)
+    int* const own = shift_total + 1 + blockIdx.x;
     __shared__ double red[256];
     T* x = inputs + offs[blockIdx.x];
     const int64_t n = sizes[blockIdx.x];
@@ -560,18 +629,25 @@ __global__ __launch_bounds__(256) void prescale_inputs_kernel(T* inputs, const i
         __syncthreads();
     }
     mx = red[0];
-    if (mx == 0.0) return;
-    int ex;
-    (void)frexp(mx, &ex);
-    ex -= 1;   // mx = m 2^ex with m in [1, 2)
-    if (ex >= -32 && ex < 32) return;
+    int ex = 0;
+    if (mx != 0.0) {
+        (void)frexp(mx, &ex);
+        ex -= 1;   // mx = m 2^ex with m in [1, 2)
+    }
+    if (mx == 0.0 || (ex >= -32 && ex < 32)) {
+        if (threadIdx.x == 0) *own = 0;
+        return;
+    }
     // the SMALLEST shift that brings the largest element into the window -- to [2^31, 2^32) from above, to
     // [2^-32, 2^-31) from below: an input with a wide range of its own (rows 2^80 apart) keeps as many of its
     // small elements -- and of the products they enter -- inside the fp32 range as the window allows
     const int shift = ex >= 32 ? ex - 31 : ex + 32;
     const double f = ldexp(1.0, -shift);
     for (int64_t i = threadIdx.x; i < n; i += 256) x[i] = scale_of(x[i], f);
-    if (threadIdx.x == 0) atomicAdd(shift_total, shift);
+    if (threadIdx.x == 0) {
+        *own = shift;
+        atomicAdd(shift_total, shift);
+    }
 }
 
 __global__ void prescale_finish_kernel(const int* shift_total, double* inscale) {

@@ -295,6 +295,35 @@ int validate_plan(ctg_plan* p) {
                             (long long)s, "ABC"[o], (long long)lo_addr, (long long)hi_addr, (long long)cap);
         }
     }
+    // (ABI 8) a run of consecutive accumulate steps goes out as one launch (accum_group_kernel): the result
+    // ranges they write must be disjoint, or that launch would race
+    for (int64_t s = 0; s < p->n_steps;) {
+        int64_t j = s;
+        std::vector<std::pair<int64_t, int64_t>> ranges;
+        for (; j < p->n_steps && p->steps[j * STEP_WORDS + W_KIND] == KIND_ACCUM; ++j) {
+            const int64_t* r = &p->steps[j * STEP_WORDS];
+            int64_t lo = r[W_C_OFF], hi = r[W_C_OFF] + (r[W_C_LEAF] >= 0 ? p->max_soff[r[W_C_LEAF]] : 0), mn;
+            hi += tab_max(p, r[W_ROWC_HI], r[W_ROW_HI_LEN], &mn);
+            lo += mn;
+            hi += tab_max(p, r[W_ROWC_LO], r[W_ROW_LO], &mn);
+            lo += mn;
+            ranges.emplace_back(lo, hi);
+        }
+        if (ranges.size() > 1) {
+            if (p->steps[s * STEP_WORDS + W_C_SPACE] != SPACE_RESULT)
+                return fail(CTG_E_INVALID, "step %lld: consecutive accumulate steps must write the result", (long long)s);
+            for (int64_t k = s; k < j; ++k)
+                if (p->steps[k * STEP_WORDS + W_C_SPACE] != p->steps[s * STEP_WORDS + W_C_SPACE])
+                    return fail(CTG_E_INVALID, "step %lld: consecutive accumulate steps in different spaces", (long long)k);
+            std::sort(ranges.begin(), ranges.end());
+            for (size_t k = 1; k < ranges.size(); ++k)
+                if (ranges[k].first <= ranges[k - 1].second)
+                    return fail(CTG_E_INVALID,
+                                "steps %lld-%lld: consecutive accumulate steps write overlapping ranges (one launch would race)",
+                                (long long)s, (long long)(j - 1));
+        }
+        s = j > s ? j : s + 1;
+    }
     if (p->has_groups) {
         // (group indices of extent 1 only: every "group" is one slice -- the plan shares nothing, and
         // ctg_exec_run_slices / ctg_exec_run_share must not hand the work to each other for ever)
@@ -994,6 +1023,13 @@ void* wide_of_step(const ctg_exec* e, int64_t s) {
     return e->d_wide + r[W_C_OFF] * 2 * kItemSize[e->plan->dtype];
 }
 
+// the input whose own upload shift an accumulate step's coefficient leaves out: the leaf its result operand names
+// (a gradient, ABI 8); -1 for the pseudo-leaf n_inputs of a forward plan's accumulate
+int accum_leaf(const ctg_plan* p, int64_t s) {
+    const int64_t leaf = p->steps[s * STEP_WORDS + W_C_LEAF];
+    return leaf >= 0 && leaf < p->n_inputs ? (int)leaf : -1;
+}
+
 
 
 // Where the arena lies in physical HBM is worth 2-3 % of a slice of a big tree (profiles/r6_process_alternation.txt: the
@@ -1134,9 +1170,9 @@ int launch_step(ctg_exec* e, int64_t s, hipStream_t stream) {
                     err = launch_rescale(p->dtype, e->d_result, p->result_elems, e->d_strip, stream);
                 if (err == hipSuccess && e->d_wide)
                     err = launch_rescale(p->dtype + 1, e->d_wide, p->result_elems, e->d_strip, stream);
-                if (err == hipSuccess) err = launch_accum(p->dtype, e->args[s], e->d_strip, wide_of_step(e, s), nullptr, stream);
+                if (err == hipSuccess) err = launch_accum(p->dtype, e->args[s], e->d_strip, wide_of_step(e, s), nullptr, -1, stream);
             } else {
-                err = launch_accum(p->dtype, e->args[s], nullptr, wide_of_step(e, s), e->d_inscale, stream);
+                err = launch_accum(p->dtype, e->args[s], nullptr, wide_of_step(e, s), e->d_inscale, accum_leaf(p, s), stream);
             }
             break;
         case KIND_STEM2: {
@@ -1297,6 +1333,10 @@ int build_groups(ctg_exec* e) {
     if (e->d_fast_items) (void)hipFree(e->d_fast_items);
     e->d_group_items = nullptr;
     e->d_fast_items = nullptr;
+    if (e->d_accum_items) (void)hipFree(e->d_accum_items);
+    e->d_accum_items = nullptr;
+    e->accum_member.assign((size_t)n, 0);
+    std::vector<AccumGroupItem> aitems;
     // LDS-resident subtrees: which steps a component's workgroup runs (none under strip_exponent)
     {
         const int rc = ctg_lds_build(e);
@@ -1359,6 +1399,22 @@ int build_groups(ctg_exec* e) {
             ++s;
             continue;
         }
+        if (!e->strip && p->steps[s * STEP_WORDS + W_KIND] == KIND_ACCUM && s + 1 < n &&
+            p->steps[(s + 1) * STEP_WORDS + W_KIND] == KIND_ACCUM) {
+            // consecutive accumulate steps (the gradients of a VJP plan): one launch; their result ranges are
+            // disjoint (validate_plan)
+            int64_t j = s;
+            uint32_t blocks = 0;
+            const int32_t item0 = (int32_t)aitems.size();
+            for (; j < n && p->steps[j * STEP_WORDS + W_KIND] == KIND_ACCUM && !e->invariant[j] && !lds_member(j); ++j) {
+                aitems.emplace_back();
+                blocks += accum_group_fill(e->args[j], wide_of_step(e, j), accum_leaf(p, j), &aitems.back(), blocks);
+                e->accum_member[j] = 1;
+            }
+            e->issue.push_back(ctg_exec::Issue{s, -3, item0, (int32_t)(j - s), blocks, e->grouped[s] != 0});
+            s = j;
+            continue;
+        }
         if (class_of(s) < 0) {
             e->issue.push_back(ctg_exec::Issue{s, -1, 0, 1, 0, e->grouped[s] != 0});
             ++s;
@@ -1411,6 +1467,10 @@ int build_groups(ctg_exec* e) {
         HIP_TRY(hipMemcpy(e->d_group_items, vitems.data(), vitems.size() * sizeof(ValuGroupItem),
                           hipMemcpyHostToDevice));
     }
+    if (!aitems.empty()) {
+        HIP_TRY(hipMalloc((void**)&e->d_accum_items, aitems.size() * sizeof(AccumGroupItem)));
+        HIP_TRY(hipMemcpy(e->d_accum_items, aitems.data(), aitems.size() * sizeof(AccumGroupItem), hipMemcpyHostToDevice));
+    }
     if (!fitems.empty()) {
         HIP_TRY(hipMalloc((void**)&e->d_fast_items, fitems.size() * sizeof(FastGroupItem)));
         HIP_TRY(hipMemcpy(e->d_fast_items, fitems.data(), fitems.size() * sizeof(FastGroupItem),
@@ -1428,6 +1488,14 @@ int launch_issue(ctg_exec* e, const ctg_exec::Issue& q, int nb, hipStream_t stre
         const hipError_t err = launch_lds_run(e->plan->dtype, e->d_lds_comps + q.item0, q.n, nb, 0, e->lds_bytes[cls], stream);
         if (err != hipSuccess)
             return fail(CTG_E_HIP, "launch of the %d LDS-resident subtrees at step %lld failed: %s", (int)q.n,
+                        (long long)q.step, hipGetErrorString(err));
+        return CTG_OK;
+    }
+    if (q.cls == -3) {
+        const hipError_t err = launch_accum_group(e->plan->dtype, e->d_accum_items + q.item0, q.n, q.blocks, nb,
+                                                  e->d_inscale, stream);
+        if (err != hipSuccess)
+            return fail(CTG_E_HIP, "launch of the %d accumulate steps grouped at step %lld failed: %s", (int)q.n,
                         (long long)q.step, hipGetErrorString(err));
         return CTG_OK;
     }
@@ -1715,6 +1783,7 @@ int ctg_exec_destroy(ctg_exec* e) {
     if (e->d_lane_b) (void)hipFree(e->d_lane_b);
     if (e->d_group_items) (void)hipFree(e->d_group_items);
     if (e->d_fast_items) (void)hipFree(e->d_fast_items);
+    if (e->d_accum_items) (void)hipFree(e->d_accum_items);
     if (e->d_stem_max) (void)hipFree(e->d_stem_max);
     if (e->d_smax_zero) (void)hipFree(e->d_smax_zero);
     if (e->d_lds_comps) (void)hipFree(e->d_lds_comps);
@@ -1823,9 +1892,11 @@ int ctg_exec_create(const ctg_plan* p, int device, void* stream, void* ext_resul
         }
         HIP_TRY_E(hipMalloc((void**)&e->d_in_tab, tab.size() * 8));
         HIP_TRY_E(hipMemcpy(e->d_in_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
-        HIP_TRY_E(hipMalloc((void**)&e->d_inscale, 2 * sizeof(double) + sizeof(int64_t)));
-        const double init[3] = {1.0, 0.0, 0.0};
-        HIP_TRY_E(hipMemcpy(e->d_inscale, init, sizeof(init), hipMemcpyHostToDevice));
+        // {2^S, S log10(2)} then ints: S and (ABI 8) each input's own shift (prescale_inputs_kernel, accum_coef)
+        std::vector<double> init(3 + (p->n_inputs + 1) / 2, 0.0);
+        init[0] = 1.0;
+        HIP_TRY_E(hipMalloc((void**)&e->d_inscale, init.size() * sizeof(double)));
+        HIP_TRY_E(hipMemcpy(e->d_inscale, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     {
         // float / complex64 results of a tree with more than one slice: the slices are summed in double
@@ -2411,7 +2482,8 @@ int ctg_exec_step_kernel(ctg_exec* e, int64_t step, char* buf, int64_t buflen) {
     } else if (r[W_KIND] == KIND_SINGLE) {
         snprintf(name, sizeof(name), "single_kernel");
     } else if (r[W_KIND] == KIND_ACCUM) {
-        snprintf(name, sizeof(name), "accum_kernel");
+        snprintf(name, sizeof(name), (size_t)step < e->accum_member.size() && e->accum_member[step] ? "accum_group_kernel"
+                                                                                                    : "accum_kernel");
     } else if (r[W_KIND] == KIND_STEM2) {
         // (the arithmetic of the step's NEXT launch: fp16 x 2 needs the producer of its big operand to be a stem
         // launch of the 16-bit pipe -- decided on the shapes here, as launch_step decides it on what ran)

@@ -1041,6 +1041,17 @@ class ContractionTree:
             self, arrays, group=group, root=root, **kwargs
         )
 
+    def contract_vjp(self, arrays, cotangent, wrt=None, order=None):
+        """Gradients of :meth:`contract`: ``G_i = sum_o h[o] dO[o] / dx_i`` for the cotangent ``h``
+        (the result's shape), summed over all slices on the device, for the leaves ``wrt`` (default:
+        all; ``None`` for the others) -- JAX's convention, nothing conjugated
+        (``HipContractor.vjp``, cotengra_amd/vjp.py).  ``contract`` itself is differentiable under
+        torch autograd; ``contract_slice``, ``gen_output_chunks``, ``contract_distributed`` /
+        ``contract_mpi`` and ``contract_resumable`` are not."""
+        from .contractor import _tree_contractor
+
+        return _tree_contractor(self, order).vjp(*arrays, cotangent=cotangent, wrt=wrt)
+
     def contract_resumable(self, arrays, checkpoint, **kwargs):
         """:meth:`contract` with a checkpoint file: the partial sum over slices
         is saved every ``every`` slices and an interrupted run continues from

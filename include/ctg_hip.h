@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CTG_ABI_VERSION 7
+#define CTG_ABI_VERSION 8
 
 /* element types of the tensors (reference tests cover all four:
  * tests/test_compute.py:102-115) */
@@ -76,7 +76,19 @@ enum {
  * member, or -- under strip_exponent, CTG_NO_LDS_RUNS=1, or when a component does not
  * fit the LDS of the device -- the member steps one by one.  ctg_plan_create validates
  * the descriptors like everything else (tables inside the blob, LDS addresses inside
- * the component's data area, global addresses inside their space). */
+ * the component's data area, global addresses inside their space).
+ *
+ * ABI 8 -- gradients (cotengra_amd/vjp.py: compile_vjp).  A VJP plan's inputs are the
+ * leaves and the cotangent; it ends each slice with one accumulate step (kind 2) per
+ * leaf whose result operand names THAT leaf (word 10 = i < n_inputs): the executor adds
+ * leaf i's slice offset, and the coefficient that undoes the upload scaling of
+ * single-precision inputs leaves input i's own power of two out (d O / d x_i carries
+ * every other input's).  A forward plan's accumulate names the pseudo-leaf n_inputs and
+ * keeps the whole coefficient.  A run of consecutive accumulate steps goes out as ONE
+ * launch (accum_group_kernel, workgroups dealt in proportion to the steps' rows; the
+ * same bits as one launch per step); ctg_plan_create rejects a plan whose consecutive
+ * accumulate steps write overlapping result ranges.  A plan with one accumulate step
+ * launches accum_kernel as before. */
 typedef struct ctg_plan_desc {
     int32_t dtype;                /* CTG_F32 .. CTG_C128 */
     int64_t n_inputs;
