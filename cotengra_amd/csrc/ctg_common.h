@@ -18,6 +18,8 @@ inline bool env_on(const char* name) {
     const char* v = getenv(name);
     return v != nullptr && v[0] != '\0' && !(v[0] == '0' && v[1] == '\0');
 }
+// The same as three states, for a switch that overrides a default in BOTH directions: -1 unset, 0 set and off, 1 on.
+inline int env_state(const char* name) { return getenv(name) == nullptr ? -1 : (env_on(name) ? 1 : 0); }
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is honoured per device: remember per
 // (kernel instantiation, device) that it was done.  `done` is a per-instantiation bit mask
@@ -207,7 +209,7 @@ struct StemArgs {
     int64_t zBM, zsBM;
     int64_t a_elems, c_elems;   // extents of the big operand and of the result (the bounds-checked
                                 // experiment build -DCTG_STEM_BOUNDS tests every gather and store)
-    // (round 6) the fp16 x 2 arithmetic (ctg_stem.hip built with -DCTG_STEM_H2: launch_stem2h): largest |component| of
+    // (round 6) the fp16 x 2 arithmetic (ctg_stem_h2.hip: launch_stem2h): largest |component| of
     // the big operand as its producer recorded it, and where this launch records that of its result (device floats)
     const float* amax;
     float* cmax;
@@ -541,15 +543,14 @@ hipError_t launch_fast_lane_consts(const StepArgs& p, const MfmaHints& h, void* 
 hipError_t launch_pair_mfma_c128(const StepArgs& p, int flags, hipStream_t stream);
 // float32 / float64 on the 16x16x4 matrix-core instructions
 hipError_t launch_pair_mfma_real(int dtype, const StepArgs& p, int flags, hipStream_t stream);
-// fused stem pair (ctg_stem.hip)
+// fused stem pair (ctg_stem.hip; kernels and shape rules: ctg_stem_impl.h)
 bool stem2_supported(const StemArgs& p);
 bool stem3_supported(const StemArgs& p);   // (a three-step tile: shape, instantiation, LDS)
-size_t stem2_lds_bytes(const StemArgs& p);
 hipError_t launch_stem2(const StemArgs& p, hipStream_t stream);
 void stem2_kernel_name(const StemArgs& p, char* buf, size_t n);
-// the same kernels in the fp16 x 2 arithmetic (round 6; StemArgs::amax / cmax)
+// the same kernels in the fp16 x 2 arithmetic (ctg_stem_h2.hip, round 6; StemArgs::amax / cmax)
 bool stem2h_supported(const StemArgs& p);
-bool stem2h_uses_h2(const StemArgs& p);   // (else the launch is the fp32 kernel of that object: no record of the result)
+bool stem2h_uses_h2(const StemArgs& p);   // does the step have a 16-bit instantiation?  Else launch_stem2h is an error: that object holds no other kernel
 bool stem2_uses_bf3(const StemArgs& p);   // the same question for launch_stem2 (bf16 x 3: records the result's largest element too)
 hipError_t launch_stem2h(const StemArgs& p, hipStream_t stream);
 void stem2h_kernel_name(const StemArgs& p, char* buf, size_t n);

@@ -52,8 +52,8 @@ struct ctg_exec {
     std::vector<ctg::StepArgs> args;  // resolved per step
     std::vector<ctg::StemArgs> stem_args;  // KIND_STEM2 steps (fused stem pairs)
     int stem_bf16x3 = 1;                   // ctg_exec_set_stem_arithmetic (default since round 4: bf16 x 3)
-    // (round 6) 2: the stem kernels multiply with two fp16 limbs and three products (ctg_stem.hip built with
-    // -DCTG_STEM_H2) where they took three bf16 limbs and six; stem_bf16x3 stays 1 then (the bf16-pipe kernels are on)
+    // (round 6) 2: the stem kernels multiply with two fp16 limbs and three products (ctg_stem_h2.hip: stem2h_kernel)
+    // where they took three bf16 limbs and six; stem_bf16x3 stays 1 then (the bf16-pipe kernels are on)
     int stem_arith = 2;
     // [3 banks][n_steps][batch][kMaxSub]: largest |component| recorded by step s in slice z of a launch sequence | of step s's
     // operand A | B (max-abs pass): smax_slot().  A slice-invariant step records into z = 0.

@@ -1264,11 +1264,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(StepArgs p, int64_t 
 // (StepArgs::bf3: ctg_exec_set_stem_arithmetic, default on) unless CTG_PAIR_BF16X3 / CTG_STEM_BF16X3 in the
 // environment say otherwise ("0" / "" = fp32 products; read at every launch, tests switch within a process).
 bool pair_bf16x3_on(const StepArgs& p) {
-    auto off = [](const char* v) { return v != nullptr && (v[0] == '\0' || (v[0] == '0' && v[1] == '\0')); };
-    const char* v = getenv("CTG_PAIR_BF16X3");
-    if (v != nullptr) return !off(v);
-    v = getenv("CTG_STEM_BF16X3");
-    if (v != nullptr) return !off(v);
+    if (const int v = env_state("CTG_PAIR_BF16X3"); v >= 0) return v == 1;
+    if (const int v = env_state("CTG_STEM_BF16X3"); v >= 0) return v == 1;
     return p.bf3 != 0;
 }
 

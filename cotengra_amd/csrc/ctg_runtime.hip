@@ -1139,6 +1139,19 @@ static bool tiled16_step(const ctg_exec* e, int64_t s) {
 }
 
 // does a launch of pair step s record its result's largest |component| (what launch_step decides, on the shapes)?
+// Does a stem step run in fp16 x 2 (launch_stem2h)?  The executor's arithmetic, not under strip_exponent (a scale per
+// step there), a shape with a 16-bit kernel, and the largest element of its big operand on record (`recorded`: the caller's
+// knowledge of the producer) or CTG_STEM_H2_ALL=1 (a max-abs pass supplies it); CTG_STEM_H2=0 in the environment says no.
+static bool stem_step_h2(const ctg_exec* e, int64_t s, bool recorded) {
+    return e->stem_arith == 2 && !e->strip && e->d_stem_max != nullptr && (recorded || env_on("CTG_STEM_H2_ALL")) &&
+           stem2h_uses_h2(e->stem_args[s]) && env_state("CTG_STEM_H2") != 0;
+}
+// ... and a long tiled step of the 16-bit pipe (pair_mfma_h2_kernel)?  `single`: one slice, no k-splits, no operand shared
+// by a slice group; CTG_PAIR_H2=0 in the environment says no.
+static bool pair_step_h2(const ctg_exec* e, bool single) {
+    return e->stem_arith == 2 && single && env_state("CTG_PAIR_H2") != 0;
+}
+
 static bool pair_records(const ctg_exec* e, int64_t s) {
     const ctg_plan* p = e->plan;
     const int64_t* r = &p->steps[s * STEP_WORDS];
@@ -1189,10 +1202,7 @@ int launch_step(ctg_exec* e, int64_t s, hipStream_t stream) {
             const bool prod_rec = prod >= 0 && prod < p->n_steps && e->stem_h2_ran[prod];
             // (CTG_STEM_H2_ALL=1, tests and diagnostics: fp16 x 2 for EVERY capable pair -- a max-abs pass over the
             // big operand supplies the scale where no producer recorded it)
-            const bool h2_all = env_on("CTG_STEM_H2_ALL");
-            bool h2 = e->stem_arith == 2 && rec && (prod_rec || h2_all) && stem2h_uses_h2(e->stem_args[s]);
-            if (h2)
-                if (const char* v = getenv("CTG_STEM_H2")) h2 = !(v[0] == '\0' || (v[0] == '0' && v[1] == '\0'));
+            const bool h2 = stem_step_h2(e, s, prod_rec);
             const bool records = h2 || (rec && stem2_uses_bf3(e->stem_args[s]));
             e->stem_h2_ran[s] = records ? 1 : 0;
             if (env_on("CTG_STEM_DEBUG"))
@@ -1241,9 +1251,7 @@ int launch_step(ctg_exec* e, int64_t s, hipStream_t stream) {
                     const StepArgs& a = e->args[s];
                     const bool single = h0.splitk <= 1 && a.zqA <= 1 && a.zqB <= 1 && !e->grouped[s] &&
                                         a.z0 + a.nz <= std::max(e->batch, 1);
-                    bool h2 = e->stem_arith == 2 && single;
-                    if (h2)
-                        if (const char* v = getenv("CTG_PAIR_H2")) h2 = !(v[0] == '\0' || (v[0] == '0' && v[1] == '\0'));
+                    const bool h2 = pair_step_h2(e, single);
                     h.h2 = h2 ? 1 : 0;
                     // (the kernel adds z0 + blockIdx.y times the stride: pointers to slot 0 of the step)
                     h.cmax = single ? e->smax_slot(0, s, 0) : nullptr;
@@ -2492,11 +2500,7 @@ int ctg_exec_step_kernel(ctg_exec* e, int64_t step, char* buf, int64_t buflen) {
                             ((p->steps[prod * STEP_WORDS + W_KIND] == KIND_STEM2 &&
                               (stem2_uses_bf3(e->stem_args[prod]) || stem2h_uses_h2(e->stem_args[prod]))) ||
                              pair_records(e, prod));
-        bool h2 = e->stem_arith == 2 && !e->strip && e->d_stem_max != nullptr && (prod16 || env_on("CTG_STEM_H2_ALL")) &&
-                  stem2h_uses_h2(e->stem_args[step]);
-        if (h2)
-            if (const char* v = getenv("CTG_STEM_H2")) h2 = !(v[0] == '\0' || (v[0] == '0' && v[1] == '\0'));
-        if (h2) stem2h_kernel_name(e->stem_args[step], name, sizeof(name));
+        if (stem_step_h2(e, step, prod16)) stem2h_kernel_name(e->stem_args[step], name, sizeof(name));
         else stem2_kernel_name(e->stem_args[step], name, sizeof(name));
     } else if (r[W_KERNEL] == KERNEL_MFMA && p->dtype == CTG_C128) {
         snprintf(name, sizeof(name), "pair_mfma_c128_kernel");
@@ -2516,10 +2520,8 @@ int ctg_exec_step_kernel(ctg_exec* e, int64_t step, char* buf, int64_t buflen) {
                      (h.vecA && h.additive32) ? "true" : "false", h.additive32 ? "true" : "false",
                      r[W_K] < MFMA_BK ? "true" : "false", r[W_K] <= 4 ? 2 : (r[W_K] <= 8 ? 4 : 8));
         else if (h.bf3 && pair_bf16x3_on(e->args[step])) {
-            bool h2 = tiled16_step(e, step) && e->stem_arith == 2 && h.splitk <= 1 && !e->grouped[step] &&
-                      e->args[step].zqA <= 1 && e->args[step].zqB <= 1;
-            if (h2)
-                if (const char* v = getenv("CTG_PAIR_H2")) h2 = !(v[0] == '\0' || (v[0] == '0' && v[1] == '\0'));
+            const bool h2 = pair_step_h2(e, tiled16_step(e, step) && h.splitk <= 1 && !e->grouped[step] &&
+                                               e->args[step].zqA <= 1 && e->args[step].zqB <= 1);
             snprintf(name, sizeof(name), "%s<128,%d,16>,%s", h2 ? "pair_mfma_h2_kernel" : "pair_mfma_bf3_kernel", h.bn,
                      h.vecA ? "true" : "false");
         }

@@ -28,7 +28,7 @@ measured slower than pair + single step on every m20 tree -- DESIGN.md section 8
 
 This module is host-side planning only: which pairs to fuse (``find_pairs``)
 and the offset tables of a fused step (``build_stem_step``); the kernel is
-``csrc/ctg_stem.hip``, the numpy restatement of its addressing
+``csrc/ctg_stem_impl.h``, the numpy restatement of its addressing
 ``oracle/plan_interp.py`` (test infrastructure).  Everything here is index
 work on powers of two: every extent is split into binary digits ("bits") and
 every table is additive over bits, which is what lets the kernel form an
@@ -52,7 +52,7 @@ G_LO_BITS = 12               # fast level of the two-level grid tables
 DESC_WORDS = 56              # header of the serialised descriptor (int64 words; 40 until ABI 4)
 DESC_MAGIC = 0x53544D33      # "STM3"
 
-# what the kernel is instantiated for (csrc/ctg_stem.hip: launch_stem2)
+# what the kernel is instantiated for (csrc/ctg_stem_impl.h: launch_stem)
 K_OK = (16, 32, 64, 128)
 N1_OK = (16, 32, 64, 128)
 N2_OK = (16, 32, 64, 128)
@@ -65,7 +65,7 @@ N2_OK = (16, 32, 64, 128)
 # the lines it fetches), C2 at the full rate; together they take the longer of the two plus a fifth
 # of the shorter.
 FUSED_MFMA_RATE = 157.3e12 * 0.73
-# ... and in the bf16 x 3 arithmetic (csrc/ctg_stem.hip: BF3; fp32 operands split into three bf16
+# ... and in the bf16 x 3 arithmetic (csrc/ctg_stem_impl.h: BF3; fp32 operands split into three bf16
 # values, products on the bf16 matrix cores -- the default since round 4, ``bf16x3_mode``): the
 # factor by which the pairs' matrix work speeds up, as measured on whole pairs (DESIGN.md section
 # 4b); tree refinement for that mode (tests/golden/gen/refine_bf3.py) prices pairs with it
@@ -142,7 +142,7 @@ def b_lds_bytes(K, N):
 
 def bf16x3_fits(K1, N1, K2, N2, rows2):
     """Does the pair's tile fit the LDS in the bf16 x 3 arithmetic (the small operands as three
-    bfloat16 limb planes: csrc/ctg_stem.hip ``stem2_lds_bytes_bf3``)?  A pair that does not runs
+    bfloat16 limb planes: csrc/ctg_stem_impl.h ``stem2_lds_bytes_bf3``)?  A pair that does not runs
     fp32 products whatever the mode (``stem2_bf3``), and is priced so."""
     q1 = (3 if N1 == 16 else 2) * N1 * ((K1 >> 4) * 48 + 8)
     q2 = (3 if N2 == 16 else 2) * N2 * ((K2 >> 3) * 24 + 8)
@@ -304,7 +304,7 @@ def geometry_one(size_dict, A, B1, c_inds):
     g = Geometry()
     g.K1, g.N1, g.K2, g.N2 = K1, N1, 0, 0
     g.nr1, g.rows2_bits, g.ng2, g.items, g.lds = nr1, 0, 0, 0, lds
-    # (B1's limb planes: csrc/ctg_stem.hip stem2_lds_bytes_one; K = N = 128 has no room and multiplies in fp32)
+    # (B1's limb planes: csrc/ctg_stem_impl.h stem2_lds_bytes_one; K = N = 128 has no room and multiplies in fp32)
     g.bf3_fits = 2 * 2 * N1 * ((K1 >> 4) * 48 + 8) + 8 * N1 + 64 <= LDS_BYTES
     g.k1 = sorted(k1, key=sa)
     g.n1 = sorted(n1, key=lambda b: _stride(B1, b))
@@ -496,7 +496,7 @@ def _find_chains(steps, size_dict, by_out, classify, unfused_seconds, gain2, min
 
 def triple_shape(geo):
     """The template arguments of ``stem2_kernel`` a three-step tile needs
-    (csrc/ctg_stem.hip: CTG_STEM_TRI): 16 columns in step 1 / middle / last, units per wave, column
+    (csrc/ctg_stem_impl.h: CTG_STEM_TRI): 16 columns in step 1 / middle / last, units per wave, column
     groups of step 1, chunks of K1, items per wave of the middle and the last step, 16-byte gathers."""
     cs1 = max(1, geo.N1 // 32)
     return (geo.N1 == 16, geo.NM == 16, geo.N2 == 16, ((1 << (geo.nr1 - 5)) * cs1) // WAVES, cs1, geo.K1 // 16,
@@ -678,7 +678,7 @@ def triples_enabled():
 def triple_lds_bytes(K1, N1, KM, NM, K2, N2, rowsM, rows2, bf16x3=True):
     """LDS of a three-step tile: the three small operands' planes, the two intermediates in ONE
     region (the second is written over the first between two barriers), the column table
-    (csrc/ctg_stem.hip: stem3_lds_bytes)."""
+    (csrc/ctg_stem_impl.h: stem3_lds_bytes)."""
     mid = 8 * max(rowsM * (KM + 4), rows2 * (K2 + 4))
     if bf16x3:
         q = ((3 if N1 == 16 else 2) * N1 * ((K1 >> 4) * 48 + 8) + (3 if NM == 16 else 2) * NM * ((KM >> 3) * 24 + 8)

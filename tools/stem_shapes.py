@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Which instantiations of the fused stem kernel (csrc/ctg_stem.hip: CTG_STEM_STATIC) the
+"""Which instantiations of the fused stem kernel (csrc/ctg_stem_impl.h: CTG_STEM_INST / CTG_STEM_GEO / CTG_STEM_ONE) the
 tree fixtures need: (PACK1, PACK2, RT1, CS1, NCH, IT2, BR1, K2Q, VEC) with their share of the work."""
 import glob
 import json
@@ -22,7 +22,7 @@ def lds_ri2(st, b2_in_regs):
 
 
 def shape(st):
-    """csrc/ctg_stem.hip: stem2_shape, restated."""
+    """csrc/ctg_stem_impl.h: stem2_shape, restated."""
     cs1 = max(1, st["N1"] // 32)
     p1, p2 = st["N1"] == 16, st["N2"] == 16
     rt1 = (1 << (st["nr1"] - 5)) * cs1 // SW
@@ -81,10 +81,10 @@ print("// single steps (RT1, CS1, NCH, VEC)")
 for key, (macs, where) in sorted(ones.items(), key=lambda kv: -kv[1][0]):
     print("O(%d, %d, %d, %s)" % (*key[:3], lo(key[3])), "// %.2e" % macs, sorted(where)[:3])
 
-# what csrc/ctg_stem.hip has: anything printed below runs the run-time-count variant (fp32) until it is added
+# what csrc/ctg_stem_impl.h has: anything printed below runs the run-time-count variant (fp32) until it is added
 import re  # noqa: E402
 
-src = open(os.path.join(ROOT, "cotengra_amd", "csrc", "ctg_stem.hip")).read()
+src = open(os.path.join(ROOT, "cotengra_amd", "csrc", "ctg_stem_impl.h")).read()
 
 
 def have(macro, letter):
@@ -99,4 +99,4 @@ def fmt(key):
 missing = [("X", fmt(k)) for k in need if fmt(k) not in have("CTG_STEM_INST", "X")]
 missing += [("G", fmt(g)) for g in geo if fmt(g) not in have("CTG_STEM_GEO", "G")]
 missing += [("O", fmt(k)) for k in ones if fmt(k) not in have("CTG_STEM_ONE", "X")]
-print("// not in csrc/ctg_stem.hip:", ", ".join("%s(%s)" % (l, ", ".join(k)) for l, k in missing) or "nothing")
+print("// not in csrc/ctg_stem_impl.h:", ", ".join("%s(%s)" % (l, ", ".join(k)) for l, k in missing) or "nothing")
