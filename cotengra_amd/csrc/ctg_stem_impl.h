@@ -99,6 +99,10 @@ constexpr int SW = 8;            // waves per workgroup
 // three limbs, 16 with two).  Four chunks under fp16 x 2 -- the K1 = 64 pairs, whose fragments come from LDS for every
 // task -- were measured (same box, alternating): 199.5 against 198.3 ms per slice, 0.6 % SLOWER; two it stays.
 constexpr int BR1_CHUNKS = 2;
+// ... on specialised waves with two column groups in step 1 a producer multiplies a task into both groups (SH1 below) and
+// would keep the fragments of both: two chunks of two groups next to four accumulators spill 17 registers, so the budget
+// counts (group, chunk) pairs there -- one chunk stays in registers, two come from LDS.
+constexpr bool stem_br1_ws(int cs1, int nch) { return (cs1 == 2 ? 2 : 1) * nch <= BR1_CHUNKS; }
 
 __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
@@ -354,9 +358,18 @@ __device__ __forceinline__ void settle(T& v) {
 
 // PACK1 / PACK2: the first / second step has 16 output columns (one tile holds Re | Im).
 // RT1: units of step 1 per wave and tile (1 or 2).  CS1: 32-column groups of step 1 -- a
-// unit is (32-row tile, column group), so 64 / 128 columns mean 128 / 64 tile rows whose
-// row tiles are each taken by 2 / 4 waves (each gathers the rows itself: the second
-// fetch comes from the L1 / L2, the matrix cores stay evenly loaded).
+// unit is (32-row tile, column group), so 64 / 128 columns mean 128 / 64 tile rows.  How the
+// units are dealt to the waves:
+//   * a wave with at least CS1 units per tile (SH1 in the body: the producers of the specialised
+//     form, 2 RT1 units each, with CS1 = 2) takes row tiles with ALL their column groups -- a task
+//     (tile, row tile, chunk) is gathered and split once and multiplied into every group's
+//     accumulators;
+//   * otherwise (the symmetric kernels and the single steps: one unit per wave with CS1 >= 2; CS1 = 4
+//     on specialised waves) a wave keeps ONE column group and each row tile is taken by CS1
+//     waves, each of which gathers and splits the rows itself.  The second gather hits in the
+//     L1 (FETCH_SIZE and the L1's requests to the L2 are the same with either dealing) but it is
+//     not free: twice the gather instructions and L1 look-ups, twice the splits -- the pairs that
+//     moved to the first dealing became 3-8 % faster by it (profiles/stem_shared_rows.txt).
 // NCH, IT2: 16-deep chunks of the first contraction and work items of step 2 per wave,
 // known at compile time -- s_waitcnt vmcnt is positional and counts stores too, so only
 // a tile whose sequence of gathers and stores is fixed lets the compiler wait for a
@@ -419,7 +432,9 @@ __device__ __forceinline__ void settle(T& v) {
 // at the same moments -- and 24 % of a tile outside them (barrier waits, scatter).  Same tile, same tables, same
 // LDS; the only serial part left is the producers' scatter between the two barriers (the consumers drain
 // their pending stores there).  A consumer has the registers for two fragment sets: the loads and splits of
-// chunk c + 1 go out before the MFMAs of chunk c.
+// chunk c + 1 go out before the MFMAs of chunk c.  Where its two items are the two column groups of ONE row tile
+// (64 / 128 columns in step 2) and K2 <= 64, the first item keeps the split rows of all chunks in registers and the
+// second multiplies them again: one LDS read and one split of the intermediate per (row tile, chunk) -- item2k.
 #ifndef CTG_STEM_WS_DEPTH
 #define CTG_STEM_WS_DEPTH 2
 #endif
@@ -450,7 +465,14 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
     static_assert(!BR1 || NCH > 0, "B1 in registers needs the chunk count at compile time");
     static_assert(K2Q == 0 || PACK2 || IT2 == 1 || RI2, "B2 in registers: one column group per wave");
     static_assert(!RI2 || (!PACK2 && !BF3 && NCH > 0 && IT2 > 0), "row-interleaved step 2: fp32, >= 32 columns, static");
-    constexpr int RTW = PW / CS1;   // row tiles the waves of step 1 cover at once
+    // SH1: a wave's units of a tile are RR1 row tiles times ALL CS1 column groups (unit m = row tile m / CS1, column group
+    // m % CS1) -- a task (tile, row tile, chunk) is gathered and split once and multiplied into every column group's
+    // accumulators.  Specialised waves, whose producers have 2 RT1_ units per tile; a wave of the symmetric kernels has
+    // fewer units than column groups in every instantiated shape and keeps ONE column group (unit m = row tile m).
+    constexpr bool SH1 = WS && CS1 > 1 && RT1 % CS1 == 0;
+    constexpr int CG1 = SH1 ? CS1 : 1;    // column groups a task is multiplied into
+    constexpr int RR1 = RT1 / CG1;        // row tiles (tasks per chunk) per wave and tile
+    constexpr int RTW = SH1 ? PW : PW / CS1;   // row tiles the waves of step 1 cover at once
     constexpr bool STATIC = NCH > 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // (K2 is a compile-time constant where B2's fragments live in registers: LDS offsets that are
@@ -499,8 +521,8 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
     const int l31 = lane & 31;
     const bool producer = !WS || wave < PW;
     const int wave1 = WS ? (wave & (PW - 1)) : wave;   // index among the waves of its role
-    const int wrt = wave1 / CS1;           // this wave's row tile (within a round of RTW)
-    const int wcol = (wave1 % CS1) * 32;   // ... and first column of step 1
+    const int wrt = SH1 ? wave1 : wave1 / CS1;           // this wave's row tile (within a round of RTW)
+    const int wcol = SH1 ? 0 : (wave1 % CS1) * 32;       // ... and first column of step 1 (SH1: of its unit 0)
 
     const int64_t z = (int64_t)p.z0 + blockIdx.y;
     const c64* __restrict__ A = (const c64*)p.A + (sload64(p.soffA + z * p.zsA) + z * p.zA);
@@ -602,12 +624,17 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
     // scatter of the step-1 accumulators: lane part of mid_row[row] + mid_col[n]
     // (RI2 with 16 columns: the lanes of columns 16-31 hold imaginary parts -> plane Im, and
     // once more negated -> plane -Im)
-    int mid_lane = 0;
-    if constexpr (!ONE) {
-        if (PACK1) mid_lane = ri_off((int)p.mid_col[l31 & 15]) + (l31 >> 4) * (RI2 ? LD2 : PLANE1) + ri_off((int)p.mid_row[4 * kk]);
-        else mid_lane = ri_off((int)p.mid_col[wcol + l31]) + ri_off((int)p.mid_row[4 * kk]);
+    // (SH1: one per column group of the wave's units)
+    int mid_lane[CG1];
+#pragma unroll
+    for (int cg = 0; cg < CG1; ++cg) {
+        mid_lane[cg] = 0;
+        if constexpr (!ONE) {
+            if (PACK1) mid_lane[cg] = ri_off((int)p.mid_col[l31 & 15]) + (l31 >> 4) * (RI2 ? LD2 : PLANE1) + ri_off((int)p.mid_row[4 * kk]);
+            else mid_lane[cg] = ri_off((int)p.mid_col[wcol + 32 * cg + l31]) + ri_off((int)p.mid_row[4 * kk]);
+        }
+        settle(mid_lane[cg]);
     }
-    settle(mid_lane);
     // (accumulator register t is row rowmap(t) = bits 0, 1, 3, 4 of t's four bits: the tables are
     // additive over binary digits, so four entries each and a few scalar adds where they are
     // used replace 16-entry arrays that did not fit the scalar registers)
@@ -619,8 +646,8 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
     int64_t one_rt[RT1];   // ONE: the result's offset of this wave's row tile, per unit
 #pragma unroll
     for (int m = 0; m < RT1; ++m) {
-        mid_rt[m] = ONE ? 0 : __builtin_amdgcn_readfirstlane(ri_off((int)sload64(p.mid_row + 32 * (wrt + RTW * m))));
-        one_rt[m] = ONE ? sload64(p.out_row + 32 * (wrt + RTW * m)) : 0;
+        mid_rt[m] = ONE ? 0 : __builtin_amdgcn_readfirstlane(ri_off((int)sload64(p.mid_row + 32 * (wrt + RTW * (m / CG1)))));
+        one_rt[m] = ONE ? sload64(p.out_row + 32 * (wrt + RTW * (m / CG1))) : 0;
     }
     // ONE: this lane's column of the result (its column of step 1)
     const int64_t one_col = ONE ? p.out_col[wcol + l31] : 0;
@@ -729,15 +756,18 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
     // Im a) to both tiles
     f32x4 b1r[BR1 && !BF3 ? NCH * 2 : 1][2];
     f32x4 b2r[K2Q > 0 && !BF3 ? K2Q : 1][PACK2 ? 1 : 2];
-    bf16x8 b1r3[BR1 && BF3 ? NCH : 1][3][2];   // BF3: [chunk][split][b1p | b1q]
+    bf16x8 b1r3[CG1][BR1 && BF3 ? NCH : 1][3][2];   // BF3: [column group][chunk][split][b1p | b1q]
+    const int q1cg = 32 * ROW1;                      // SH1: from a column group's fragments to the next one's
     if constexpr (BR1 && BF3) {
 #pragma unroll
-        for (int c = 0; c < NCH; ++c)
+        for (int cg = 0; cg < CG1; ++cg)
 #pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                b1r3[c][q][0] = *(const bf16x8*)(q1p + c * 48 + q * 8);
-                b1r3[c][q][1] = *(const bf16x8*)(q1q + c * 48 + q * 8);
-            }
+            for (int c = 0; c < NCH; ++c)
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    b1r3[cg][c][q][0] = *(const bf16x8*)(q1p + cg * q1cg + c * 48 + q * 8);
+                    b1r3[cg][c][q][1] = *(const bf16x8*)(q1q + cg * q1cg + c * 48 + q * 8);
+                }
     }
     if constexpr (BR1 && !BF3) {
 #pragma unroll
@@ -798,7 +828,7 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
             pend3 = sload64(p.chunk_a + ic);
             if (++ic == nch) {
                 ic = 0;
-                if (++im == RT1) {
+                if (++im == RR1) {
                     im = 0;
                     ig += tile_step;
                 }
@@ -926,7 +956,7 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
                 re[j] = r[j].re;
                 im[j] = r[j].im;
             }
-            bf16x8 r3[3], i3[3], n3[3], bp3[3], bq3[3];
+            bf16x8 r3[3], i3[3], n3[3], bp3[CG1][3], bq3[CG1][3];
             AR::split(re, r3, h2_sa);
             AR::split(im, i3, h2_sa);
             __builtin_amdgcn_sched_barrier(0);
@@ -935,12 +965,15 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 if (!PACK1 && !XM1) n3[q] = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, i3[q]) ^ 0x80008000u);
-                if constexpr (BR1) {
-                    bp3[q] = b1r3[ch][q][0];
-                    bq3[q] = b1r3[ch][q][1];
-                } else {
-                    bp3[q] = *(const bf16x8*)(q1p + ch * 48 + q * 8);
-                    bq3[q] = *(const bf16x8*)(q1q + ch * 48 + q * 8);
+#pragma unroll
+                for (int cg = 0; cg < CG1; ++cg) {
+                    if constexpr (BR1) {
+                        bp3[cg][q] = b1r3[cg][ch][q][0];
+                        bq3[cg][q] = b1r3[cg][ch][q][1];
+                    } else {
+                        bp3[cg][q] = *(const bf16x8*)(q1p + cg * q1cg + ch * 48 + q * 8);
+                        bq3[cg][q] = *(const bf16x8*)(q1q + cg * q1cg + ch * 48 + q * 8);
+                    }
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -954,18 +987,28 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
             for (int t = 0; t < 6; t += AR::t_step(t)) {
                 const int ta = bf3_ta(t), tb = bf3_tb(t);
                 if (PACK1) {
-                    ax[m] = AR::mfma(r3[ta], bp3[tb], (fresh && t == 0) ? zero16 : ax[m]);
-                    ax[m] = AR::mfma(i3[ta], bq3[tb], ax[m]);
+                    ax[m] = AR::mfma(r3[ta], bp3[0][tb], (fresh && t == 0) ? zero16 : ax[m]);
+                    ax[m] = AR::mfma(i3[ta], bq3[0][tb], ax[m]);
                 } else if constexpr (XM1) {
-                    ax[m] = AR::mfma(r3[ta], bp3[tb], (fresh && t == 0) ? zero16 : ax[m]);
-                    ay[m] = AR::mfma(r3[ta], bq3[tb], (fresh && t == 0) ? zero16 : ay[m]);
-                    axm[m] = AR::mfma(i3[ta], bq3[tb], (fresh && t == 0) ? zero16 : axm[m]);
-                    ay[m] = AR::mfma(i3[ta], bp3[tb], ay[m]);
+                    ax[m] = AR::mfma(r3[ta], bp3[0][tb], (fresh && t == 0) ? zero16 : ax[m]);
+                    ay[m] = AR::mfma(r3[ta], bq3[0][tb], (fresh && t == 0) ? zero16 : ay[m]);
+                    axm[m] = AR::mfma(i3[ta], bq3[0][tb], (fresh && t == 0) ? zero16 : axm[m]);
+                    ay[m] = AR::mfma(i3[ta], bp3[0][tb], ay[m]);
                 } else {
-                    ax[m] = AR::mfma(r3[ta], bp3[tb], (fresh && t == 0) ? zero16 : ax[m]);
-                    ay[m] = AR::mfma(r3[ta], bq3[tb], (fresh && t == 0) ? zero16 : ay[m]);
-                    ax[m] = AR::mfma(n3[ta], bq3[tb], ax[m]);
-                    ay[m] = AR::mfma(i3[ta], bp3[tb], ay[m]);
+                    // (SH1: m is the task's row tile; the same A fragments go into the units of all its column groups)
+                    // (each accumulator sees its four products in the order of the one-group kernel)
+#pragma unroll
+                    for (int cg = 0; cg < CG1; ++cg) {
+                        const int u = m * CG1 + cg;
+                        ax[u] = AR::mfma(r3[ta], bp3[cg][tb], (fresh && t == 0) ? zero16 : ax[u]);
+                        ay[u] = AR::mfma(r3[ta], bq3[cg][tb], (fresh && t == 0) ? zero16 : ay[u]);
+                    }
+#pragma unroll
+                    for (int cg = 0; cg < CG1; ++cg) {
+                        const int u = m * CG1 + cg;
+                        ax[u] = AR::mfma(n3[ta], bq3[cg][tb], ax[u]);
+                        ay[u] = AR::mfma(i3[ta], bp3[cg][tb], ay[u]);
+                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (DRAIN)
@@ -1023,7 +1066,7 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
     auto scatter = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int m = 0; m < RT1; ++m) {
-            float* dst = mid + (mid_lane + mid_rt[m]);
+            float* dst = mid + (mid_lane[m % CG1] + mid_rt[m]);
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
                 dst[mid_t(t)] = XM1 ? ax[m][t] - axm[m][t] : ax[m][t];
@@ -1304,6 +1347,82 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
             if constexpr (!decltype(defer_tag)::value) drain(0, NST, std::integral_constant<int, 0>{}, scaled_tag);
         }
     };
+    // Specialised waves, two items per consumer that SHARE their row tile (items wave1 and wave1 + PW of a tile with at
+    // most PW row tiles: 64 or 128 columns in step 2) and a second contraction of NC <= 4 chunks: the first item reads and
+    // splits the rows of the intermediate as item2 does and KEEPS the fragments of all chunks (16 registers each); the
+    // second item multiplies them by its own column group's B' -- no LDS read of A', no split.  MFMAs and stores of both
+    // items are item2's, in item2's order.
+    auto item2k = [&](auto nc_tag, int item0, int64_t c_row, auto scaled_tag) __attribute__((always_inline)) {
+        constexpr int NC = decltype(nc_tag)::value;
+        constexpr bool SC = decltype(scaled_tag)::value;
+        const int cg0 = item0 / n_rt2, rt2 = item0 - cg0 * n_rt2;
+        const int cgs = PW / n_rt2;   // the second item's column group is cg0 + cgs
+        const int bI = N2 * ROW2;
+        const float* aRf = mid + (rt2 * 32 + l31) * LD2 + kk * 8;
+        struct FragA { bf16x8 ar[3], ai[3]; };
+        struct FragB { bf16x8 br[3], bi[3]; };
+        FragA AK[NC];
+        FragB BF[2];
+        f32x16 cx, cy, cxm;
+        auto load_a = [&](FragA& F, int c) __attribute__((always_inline)) {
+            const f32x4 r0 = *(const f32x4*)(aRf + 16 * c), r1 = *(const f32x4*)(aRf + 16 * c + 4);
+            const f32x4 i0 = *(const f32x4*)(aRf + PLANE + 16 * c), i1 = *(const f32x4*)(aRf + PLANE + 16 * c + 4);
+            const float re8[8] = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
+            const float im8[8] = {i0[0], i0[1], i0[2], i0[3], i1[0], i1[1], i1[2], i1[3]};
+            AR::split(re8, F.ar, h2_st);
+            AR::split(im8, F.ai, h2_st);
+        };
+        auto load_b = [&](FragB& F, const unsigned short* bR, int c) __attribute__((always_inline)) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                F.br[q] = *(const bf16x8*)(bR + c * 48 + q * 8);
+                F.bi[q] = *(const bf16x8*)(bR + bI + c * 48 + q * 8);
+            }
+        };
+        auto mul = [&](const FragA& A_, const FragB& B_, bool first) __attribute__((always_inline)) {
+            f32x16 zero16;
+#pragma unroll
+            for (int u = 0; u < 16; ++u) zero16[u] = 0.f;
+#pragma unroll
+            for (int t = 0; t < 6; t += AR::t_step(t)) {
+                const int ta = bf3_ta(t), tb = bf3_tb(t);
+                cx = AR::mfma(A_.ar[ta], B_.br[tb], (first && t == 0) ? zero16 : cx);
+                cy = AR::mfma(A_.ar[ta], B_.bi[tb], (first && t == 0) ? zero16 : cy);
+                cxm = AR::mfma(A_.ai[ta], B_.bi[tb], (first && t == 0) ? zero16 : cxm);
+                cy = AR::mfma(A_.ai[ta], B_.br[tb], cy);
+            }
+        };
+        // the accumulators become the item's pending stores
+        auto emit = [&](int cg) __attribute__((always_inline)) {
+            pdst = C + 2 * (c_row + out_lane + oc_s[cg * 32 + l31]);
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                float2 v;
+                const float xr = cx[t] - cxm[t];
+                v.x = SC ? xr * alpha * alpha2 : xr;
+                v.y = SC ? cy[t] * alpha * alpha2 : cy[t];
+                h2_vmax = fmaxf(h2_vmax, fmaxf(fabsf(v.x), fabsf(v.y)));
+                pv[t] = v;
+            }
+        };
+        static_for<0, 2>([&](auto gi) __attribute__((always_inline)) {
+            constexpr int G = decltype(gi)::value;
+            const int cg = cg0 + G * cgs;
+            const unsigned short* bR = Q2 + (cg * 32 + l31) * ROW2 + kk * 24;
+            if constexpr (G == 1) drain(0, NST, std::integral_constant<int, 0>{}, scaled_tag);   // the first item's stores
+            if constexpr (G == 0) load_a(AK[0], 0);
+            load_b(BF[0], bR, 0);
+            static_for<0, NC>([&](auto ci) __attribute__((always_inline)) {
+                constexpr int CH = decltype(ci)::value;
+                if constexpr (CH + 1 < NC) {
+                    if constexpr (G == 0) load_a(AK[CH + 1], CH + 1);
+                    load_b(BF[(CH + 1) & 1], bR, CH + 1);
+                }
+                mul(AK[CH], BF[CH & 1], CH == 0);
+            });
+            emit(cg);
+        });
+    };
     // three-step tile: work item i of the middle stage -- (32 rows of the first intermediate) x BM's
     // column group into mx / my (the loops of item2, with the middle step's operand) ...
     f32x16 mx[TRI ? ITM : 1], my[TRI ? ITM : 1];
@@ -1434,14 +1553,14 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
     auto run = [&](auto scaled_tag) __attribute__((always_inline)) {
     if constexpr (WS) {
         // ---- specialised waves: producers one tile ahead of the consumers ---------------------------------
-        constexpr int NT = RT1 * NCH;            // tasks per tile and producer
+        constexpr int NT = RR1 * NCH;            // tasks per tile and producer (SH1: one per row tile and chunk)
         constexpr int U = (NT % GD == 0) ? 1 : ((2 * NT) % GD == 0 ? 2 : 4);   // tiles per pass: the gather register sets rotate
         static_assert((U * NT) % GD == 0, "a pass of U tiles returns to gather set 0");
         // step 1 of the producer's next tile: every unit, every chunk (no stores on this side: a wait for a
         // gather counts gathers only)
         auto step1 = [&](auto slot0_tag) __attribute__((always_inline)) {
             constexpr int SLOT0 = decltype(slot0_tag)::value;
-            static_for<0, RT1>([&](auto mi) __attribute__((always_inline)) {
+            static_for<0, RR1>([&](auto mi) __attribute__((always_inline)) {
                 constexpr int M = decltype(mi)::value;
                 static_for<0, NCH>([&](auto ci) __attribute__((always_inline)) {
                     constexpr int CH = decltype(ci)::value;
@@ -1454,6 +1573,19 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
         auto step2 = [&](int64_t gc) __attribute__((always_inline)) {
             const int64_t c_tile = tile_c(gc);
             int64_t c_rows[IT2];
+            if constexpr (IT2 == 2 && XM2) {
+                if (n_rt2 <= PW) {   // (uniform: the wave's two items are one row tile's)
+                    const int nc = K2 >> 4;
+                    if (nc == 4) {
+                        item2k(std::integral_constant<int, 4>{}, wave1, item_row(wave1, c_tile), scaled_tag);
+                        return;
+                    }
+                    if (nc == 2) {
+                        item2k(std::integral_constant<int, 2>{}, wave1, item_row(wave1, c_tile), scaled_tag);
+                        return;
+                    }
+                }
+            }
             static_for<0, IT2>([&](auto ii) __attribute__((always_inline)) {
                 c_rows[decltype(ii)::value] = item_row(wave1 + PW * decltype(ii)::value, c_tile);
             });
@@ -2089,7 +2221,8 @@ static void stem_kernel_name(const StemArgs& p, char* buf, size_t n) {
                      s.nch, s.it2, tf(s.nch <= BR1_CHUNKS), tf(s.vec));
         else   // (..., XM, LM -- reserved --, WS)
             snprintf(buf, n, "%s<%s,%s,%d,%d,%d,%d,%s,0,%s,true,false,false,0,false,true,false,%s>", kn, tf(s.p1), tf(s.p2),
-                     s.rt1, s.cs1, s.nch, s.it2, tf(s.nch <= BR1_CHUNKS), tf(s.vec), tf(form >= 3));
+                     s.rt1, s.cs1, s.nch, s.it2, tf(form >= 3 ? stem_br1_ws(s.cs1, s.nch) : s.nch <= BR1_CHUNKS), tf(s.vec),
+                     tf(form >= 3));
     }
     else if (stem2_variant(p))
         snprintf(buf, n, "%s<%s,%s,%d,%d,%d,%d,%s,%d,%s,false,%s,false>", kn, tf(s.p1), tf(s.p2), s.rt1, s.cs1, s.nch,
@@ -2157,7 +2290,7 @@ static hipError_t launch_stem(const StemArgs& p, hipStream_t stream) {
     if (s.p1 == P1 && s.p2 == P2 && s.rt1 == R && s.cs1 == CS && s.nch == NC && s.it2 == IT && s.vec == V) {             \
         if constexpr (AR::max_form >= 3 && IT <= 2 && (P1 || R == 1) && (P2 || IT < 2)) {                                \
             if (form == 3)                                                                                               \
-                return launch_stem2_t<AR, P1, P2, R, CS, NC, IT, (NC <= BR1_CHUNKS), 0, V, true, false, true, true>(p, stream);  \
+                return launch_stem2_t<AR, P1, P2, R, CS, NC, IT, stem_br1_ws(CS, NC), 0, V, true, false, true, true>(p, stream);  \
         }                                                                                                                \
         if constexpr (IT < 4) {                                                                                          \
             if (form == 1)                                                                                               \
