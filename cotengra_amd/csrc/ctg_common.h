@@ -596,8 +596,9 @@ struct SliceMeta {
     double* fac;             // strip_exponent: per-step max|.| scalars (or null)
     const int32_t* fac_zero; // [n_fac] 1: zero the scalar at slice start (per-slice pair steps)
     int64_t n_fac;
-    // (round 6) fp16 x 2 stem kernels: the largest element each stem step recorded for its result; the slots of
-    // per-slice steps start every slice at zero (smax_zero[i] = 1), what a group shares or is slice-invariant keeps its own
+    // (round 6) fp16 x 2 stem kernels: the largest element each stem step recorded for its result; the prologue sets
+    // the slots of the steps launched behind it to zero (smax_zero[i] = 1: one of the three masks of ctg_exec::d_smax_zero
+    // -- a slice, a slice that reuses its group's shared steps, the slice-invariant steps of a new upload)
     float* smax;
     const int32_t* smax_zero;
     int64_t n_smax;

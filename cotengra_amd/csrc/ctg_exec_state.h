@@ -57,10 +57,21 @@ struct ctg_exec {
     int stem_arith = 2;
     // [3 banks][n_steps][batch][kMaxSub]: largest |component| recorded by step s in slice z of a launch sequence | of step s's
     // operand A | B (max-abs pass): smax_slot().  A slice-invariant step records into z = 0.
+    // A producer only raises its record, so the prologue in front of it sets the record to zero: the one before a
+    // slice resets the per-slice steps' and the group-shared steps', the one before the slice-invariant steps of a
+    // new upload every record -- what an executor returns never depends on what it ran before.
     float* d_stem_max = nullptr;
-    int32_t* d_smax_zero = nullptr;        // (same shape) which of them start a slice at zero
+    // [3 masks][n_steps][batch][kMaxSub]: the records of bank 0 that a prologue sets to zero -- 0: before every
+    // step of a slice, 1: before a slice that reuses its group's shared steps, 2: before the slice-invariant steps
+    int32_t* d_smax_zero = nullptr;
     float* smax_slot(int bank, int64_t s, int64_t z) const {
         return d_stem_max + (((int64_t)bank * plan_steps + s) * (batch > 1 ? batch : 1) + z) * ctg::kMaxSub;
+    }
+    // `meta` for a prologue that resets the records of mask `which` (meta itself: mask 0)
+    ctg::SliceMeta meta_resetting(int which) const {
+        ctg::SliceMeta m = meta;
+        if (m.smax) m.smax_zero = d_smax_zero + (int64_t)which * m.n_smax;
+        return m;
     }
     int64_t plan_steps = 0;                // (= plan->n_steps, for smax_slot)
     std::vector<char> rec_wanted;          // the record of step s's largest |component| has a reader (build_hints)

@@ -1653,7 +1653,10 @@ int run_grouped(ctg_exec* e, const int64_t* ids, size_t n_ids) {
     }
     for (const auto& ks : order) {
         const bool fresh = ks.first != e->group_key;
-        hipError_t err = launch_prologue(e->meta, e->d_state, e->d_soff, ks.second, e->stream, 1, 1);
+        // (a slice that reuses its group's shared steps keeps their records; the first slice of a group resets them
+        // with its own, so that a group's result does not depend on the groups before it)
+        hipError_t err = launch_prologue(fresh ? e->meta : e->meta_resetting(1), e->d_state, e->d_soff, ks.second,
+                                         e->stream, 1, 1);
         if (err != hipSuccess) return fail(CTG_E_HIP, "prologue launch failed: %s", hipGetErrorString(err));
         e->group_key = -1;   // (until the shared steps of this key are all launched)
         for (const ctg_exec::Issue& q : fresh ? e->issue : e->issue_reuse) {
@@ -1672,11 +1675,15 @@ int run_grouped(ctg_exec* e, const std::vector<int64_t>& ids) { return run_group
 int run_invariants(ctg_exec* e) {
     if (e->invariants_ready) return CTG_OK;
     const ctg_plan* p = e->plan;
+    // (new inputs or options: an unsliced tree launches its prologue once more, ctg_exec_run_slices -- besides the
+    // leaf offsets it resets the records of the largest |component| that the previous inputs left, see ctg_exec_create)
+    e->soff_static = false;
     bool any = false;
     for (int64_t s = 0; s < p->n_steps; ++s) any = any || e->invariant[s];
     if (any) {
-        // invariant operands are never slice dependent, but kernels read *soff
-        hipError_t err = launch_prologue(e->meta, e->d_state, e->d_soff, 0, e->stream);
+        // invariant operands are never slice dependent, but kernels read *soff; every record starts at zero (the
+        // slice prologues leave the invariant steps' alone)
+        hipError_t err = launch_prologue(e->meta_resetting(2), e->d_state, e->d_soff, 0, e->stream);
         if (err != hipSuccess)
             return fail(CTG_E_HIP, "prologue launch failed: %s", hipGetErrorString(err));
         if (e->strip)
@@ -1858,7 +1865,10 @@ int ctg_exec_create(const ctg_plan* p, int device, void* stream, void* ext_resul
             // the shared steps go out once per group (nz / d), what the others read of them sits with
             // the group's first slice (StepArgs.zqA / zqB).  Fused stem steps do not take part (their
             // kernel has no z quantum): such plans contract slice by slice, and so does one whose group
-            // does not fit a launch.
+            // does not fit a launch.  So no step that a group shares records its largest |component| in a batched
+            // launch -- a shared pair step never records (pair_records), a plan with a stem step never batches its
+            // groups (checked below) --, and the groups of a launch cannot meet in one record (a shared stem step
+            // records into slot 0 whatever the group).
             int64_t d = 1;
             for (int64_t j = 0; j < p->n_sliced; ++j)
                 if (p->slice_group[j] && p->slice_fixed[j] < 0) d *= p->slice_sizes[j];
@@ -1870,6 +1880,8 @@ int ctg_exec_create(const ctg_plan* p, int device, void* stream, void* ext_resul
                 e->batch = (int)(e->batch / d * d);
                 e->group_d = (int)d;
             }
+            if (e->group_d > 1 && stems)
+                return bail(fail(CTG_E_INVALID, "a plan with fused stem steps cannot batch its slice groups"));
         }
         // what the plan alone says about batching (no environment, no free-memory
         // query): the k-splits of its steps are chosen for launches of this many
@@ -1978,16 +1990,26 @@ int ctg_exec_create(const ctg_plan* p, int device, void* stream, void* ext_resul
             // (three banks of n_steps: recorded by the step | max-abs pass over its operand A | ... B)
             const int64_t nb = std::max<int64_t>(e->batch, 1);
             e->plan_steps = p->n_steps;
-            // (what the slice prologue resets: the records of bank 0 of the steps that can record -- stem launches and
-            // matrix-core pair steps --; the max-abs banks are cleared where a pass is launched)
-            std::vector<int32_t> sz((size_t)(3 * std::max<int64_t>(p->n_steps, 1) * nb * kMaxSub), 0);
+            // A record is only ever raised (atomicMax), so it must be zero before its producer runs again: a prologue
+            // resets the records of bank 0 of the steps that can record -- stem launches and matrix-core pair steps --
+            // that are launched after it (the max-abs banks are cleared where a pass is launched).  Three masks of
+            // the size of bank 0, one per kind of prologue (ctg_exec::meta_resetting):
+            //   0  before every step of a slice: the per-slice steps and what a slice group shares
+            //   1  before a slice that finds its group's shared steps done (issue_reuse): the per-slice steps
+            //   2  before the slice-invariant steps of a new upload / option: every record
+            const size_t bank = (size_t)(std::max<int64_t>(p->n_steps, 1) * nb * kMaxSub);
+            std::vector<int32_t> sz(3 * bank, 0);
             for (int64_t st = 0; st < p->n_steps; ++st) {
                 const int64_t* rs = &p->steps[st * STEP_WORDS];
                 stems = stems || rs[W_KIND] == KIND_STEM2;
                 const bool can = rs[W_KIND] == KIND_STEM2 || (rs[W_KIND] == KIND_PAIR && rs[W_KERNEL] == KERNEL_MFMA);
-                // (slice-invariant steps and what a slice group shares keep their record across slices)
-                if (can && !e->invariant[st] && !e->grouped[st])
-                    for (int64_t z = 0; z < nb * kMaxSub; ++z) sz[(size_t)(st * nb * kMaxSub + z)] = 1;
+                if (!can) continue;
+                for (int64_t z = 0; z < nb * kMaxSub; ++z) {
+                    const size_t at = (size_t)(st * nb * kMaxSub + z);
+                    sz[at] = e->invariant[st] ? 0 : 1;
+                    sz[bank + at] = (e->invariant[st] || e->grouped[st]) ? 0 : 1;
+                    sz[2 * bank + at] = 1;
+                }
             }
             e->stem_h2_ran.assign(p->n_steps, 0);
             if (e->wave_member.size() != (size_t)p->n_steps) e->wave_member.assign(p->n_steps, 0);
@@ -2191,7 +2213,9 @@ int ctg_exec_run_slices(ctg_exec* e, int64_t first, int64_t count, int64_t strid
     }
     // slices sid, sid + stride, ... (nb of them) through one launch sequence
     auto eager = [&](int64_t sid, int nb = 1) -> int {
-        // (an unsliced tree has one set of leaf offsets -- all zero: computed once)
+        // (an unsliced tree has one set of leaf offsets -- all zero: computed once per upload or change of options,
+        // run_invariants clears the flag -- the same launch sets the records of the largest |component| to zero, and
+        // mask 0 is all of them there: an unsliced tree has no slice-invariant and no group-shared step)
         if (p->n_sliced > 0 || e->strip || !e->soff_static) {
             hipError_t err = launch_prologue(e->meta, e->d_state, e->d_soff, sid, e->stream, nb, stride);
             if (err != hipSuccess)

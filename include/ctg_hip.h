@@ -156,7 +156,11 @@ int ctg_exec_set_stream(ctg_exec* exec, void* stream);
  * input_sizes[i] contiguous row-major elements.  Replaces passing `*arrays`
  * to the contractor (contract.py:718, 779-780) / `reset_operands`
  * (contract.py:916).  `_host` synchronises the stream before returning;
- * `_device` enqueues device-to-device copies. */
+ * `_device` enqueues device-to-device copies.
+ * An executor may be uploaded and run any number of times: what it returns for
+ * (inputs uploaded, arithmetic and options set, slices asked for) is the same
+ * bits as a new executor of the same plan would return for them, whatever was
+ * uploaded, run or set on it before. */
 int ctg_exec_upload_inputs_host(ctg_exec* exec, const void* const* ptrs);
 int ctg_exec_upload_inputs_device(ctg_exec* exec, const void* const* ptrs);
 

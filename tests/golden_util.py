@@ -184,3 +184,75 @@ STEM_CASES = [
     (17, [(3, 3), (5, 7), (5, 5)]),                    # k32 n128 | k32 n32: four waves per row tile
     (18, [(3, 3), (4, 7), (5, 4)]),                    # k16 n128 | k32 n16
 ]
+
+
+# ---------------------------------------------------------------------- #
+# helpers shared by the GPU modules (tests/test_gpu_round4.py, test_gpu_round6.py, test_gpu_exec_history.py)
+# ---------------------------------------------------------------------- #
+
+# the small golden trees in which the planner finds LDS-resident subtrees, and the sliced ones for the slice groups
+LDS_TREES = ["C1_rand10_d4", "C2_lattice8x8_d4", "lattice8x8_sliced", "lattice4x4_sliced", "preproc_s0_a", "preproc_s1",
+             "rand_s42_r3_o2_hi1_ho2", "rand_s666_r3_o2_hi2_ho2_sliced", "rand_s42_r2_o2_hi0_ho2_outsliced",
+             "project_1", "C5_hyper200"]
+GROUP_CASES = [c["name"] for c in cases("tree")
+               if c["name"] in ("lattice4x4_sliced", "lattice8x8_sliced", "preproc_s0_ac", "preproc_s1_ac")
+               or (c["name"].startswith("rand_") and c["name"].endswith("sliced"))]
+
+
+def chain_tree(R, K, N, N2=None):
+    """a[R, K] b[K, N] (c[N, N2]): one long tiled step, or two of them in a chain (the second one's big operand
+    produced -- and its largest element recorded -- by the first)."""
+    if N2 is None:
+        return ca.ContractionTree.from_path([("a", "b"), ("b", "c")], ("a", "c"), dict(a=R, b=K, c=N), path=[(0, 1)])
+    return ca.ContractionTree.from_path([("a", "b"), ("b", "c"), ("c", "d")], ("a", "d"), dict(a=R, b=K, c=N, d=N2),
+                                        path=[(0, 1), (0, 1)])
+
+
+def cplx(rng, *shape):
+    return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype("complex64")
+
+
+# what the library reads from the environment to pick an arithmetic, a slice batch, a captured graph or slice groups
+ARITH_ENV = ("CTG_STEM_ARITH", "CTG_STEM_BF16X3", "CTG_STEM_H2", "CTG_STEM_H2_ALL", "CTG_PAIR_BF16X3", "CTG_PAIR_H2",
+             "CTG_NO_PAIR_RECORD", "CTG_GRAPH", "CTG_SLICE_BATCH", "CTG_SLICE_GROUPS", "CTG_NO_BATCHED_GROUPS")
+
+
+def fuse_whatever_fits(monkeypatch, h2_all=True):
+    """The pairing model takes every stem pair the kernel can run, and nothing in the environment names an arithmetic.
+    By default the FIRST pair of a stem -- its big operand comes from a kernel that records no maximum -- is multiplied
+    in bf16 x 3; ``h2_all`` gives every capable pair fp16 x 2 (a max-abs pass supplies the scale)."""
+    from cotengra_amd import stem
+    monkeypatch.setattr(stem, "gather_rate", lambda run_bytes: 5.4e12)
+    for k in ARITH_ENV:
+        monkeypatch.delenv(k, raising=False)
+    if h2_all:
+        monkeypatch.setenv("CTG_STEM_H2_ALL", "1")
+
+
+def groups_everywhere(monkeypatch):
+    """Slice groups wherever a step is independent of a sliced index, whatever the model says they save."""
+    from cotengra_amd import plan as P
+
+    monkeypatch.delenv("CTG_SLICE_GROUPS", raising=False)
+    monkeypatch.setattr(P, "GROUP_MIN_WIDTH", 1)
+    monkeypatch.setattr(P, "GROUP_MIN_SAVING", 0.0)
+
+
+# An input whose largest |component| lies outside [2^-32, 2^32) is brought back to the edge of that window at upload
+# (prescale_inputs_kernel): a scale that leaves the window never reaches a kernel.
+UPLOAD_WINDOW_LOG2 = 32
+
+
+def assert_in_upload_window(x):
+    x = np.asarray(x)
+    top = float(max(np.abs(x.real).max(), np.abs(x.imag).max())) if np.iscomplexobj(x) else float(np.abs(x).max())
+    assert 2.0 ** -UPLOAD_WINDOW_LOG2 <= top < 2.0 ** UPLOAD_WINDOW_LOG2, ("the upload would normalise this scale away", top)
+
+
+def scaled_in_window(x, log2):
+    """``x * 2^log2`` (an exact power of two, the dtype kept), its largest |component| asserted to stay inside the
+    upload window -- the kernels see the scale."""
+    assert int(log2) == log2
+    y = (np.asarray(x) * np.asarray(2.0 ** int(log2), dtype=np.asarray(x).real.dtype)).astype(np.asarray(x).dtype)
+    assert_in_upload_window(y)
+    return y

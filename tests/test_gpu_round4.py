@@ -513,18 +513,12 @@ def test_slice_groups_full_width_bit_identical(monkeypatch):
     assert res["1"] == res["0"] and res["1"] != 0
 
 
-GROUP_CASES = [c["name"] for c in G.cases("tree")
-               if c["name"] in ("lattice4x4_sliced", "lattice8x8_sliced", "preproc_s0_ac", "preproc_s1_ac")
-               or (c["name"].startswith("rand_") and c["name"].endswith("sliced"))]
+GROUP_CASES = G.GROUP_CASES
 
 
 @pytest.fixture
 def groups_everywhere(monkeypatch):
-    from cotengra_amd import plan as P
-
-    monkeypatch.delenv("CTG_SLICE_GROUPS", raising=False)
-    monkeypatch.setattr(P, "GROUP_MIN_WIDTH", 1)
-    monkeypatch.setattr(P, "GROUP_MIN_SAVING", 0.0)
+    G.groups_everywhere(monkeypatch)
 
 
 @pytest.mark.parametrize("name", GROUP_CASES)

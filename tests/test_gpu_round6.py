@@ -38,9 +38,7 @@ def contract(tree, arrays, **kw):
     return np.asarray(out), info
 
 
-LDS_TREES = ["C1_rand10_d4", "C2_lattice8x8_d4", "lattice8x8_sliced", "lattice4x4_sliced", "preproc_s0_a", "preproc_s1",
-             "rand_s42_r3_o2_hi1_ho2", "rand_s666_r3_o2_hi2_ho2_sliced", "rand_s42_r2_o2_hi0_ho2_outsliced",
-             "project_1", "C5_hyper200"]
+LDS_TREES = G.LDS_TREES
 
 
 @pytest.mark.parametrize("name", LDS_TREES)
@@ -277,13 +275,8 @@ def test_plain_c_driver_fails_loudly_without_rccl(tmp_path):
 
 @pytest.fixture
 def fuse_whatever_fits(monkeypatch):
-    from cotengra_amd import stem
-    monkeypatch.setattr(stem, "gather_rate", lambda run_bytes: 5.4e12)
-    for k in ("CTG_STEM_ARITH", "CTG_STEM_BF16X3", "CTG_STEM_H2"):
-        monkeypatch.delenv(k, raising=False)
-    # (by default the FIRST pair of a stem -- its big operand comes from a kernel that records no maximum -- is
-    # multiplied in bf16 x 3; the kernel tests want every capable pair in fp16 x 2: a max-abs pass supplies the scale)
-    monkeypatch.setenv("CTG_STEM_H2_ALL", "1")
+    # (the kernel tests want every capable pair in fp16 x 2: a max-abs pass supplies the first pair's scale)
+    G.fuse_whatever_fits(monkeypatch, h2_all=True)
 
 
 def _stem_names(fn, arrays):
@@ -369,10 +362,13 @@ def test_single_stem_steps_in_fp16x2(case, fuse_whatever_fits, monkeypatch):
 
 
 def test_fp16x2_scales_are_exact_powers_of_two(fuse_whatever_fits):
-    """Inputs alternately scaled by 2^+40 and 2^-40, the big state by 2^-90: every scale the kernels take out is a
-    power of two found from the data, so the limbs -- and the result, up to the power put back in -- are the SAME
-    BITS as in the plain run; a chain of pairs whose intermediates' magnitudes differ by 2^40 from one pair to the
-    next also checks that every pair scales with ITS operand's record, not a stale one."""
+    """Inputs alternately scaled by 2^+40 and 2^-40, the big state by 2^-90: every one of these scales lies outside the
+    upload window [2^-32, 2^32), so the upload takes it out as an exact power of two (prescale_inputs_kernel) and puts it
+    back in at the end -- the kernels see the magnitudes of the plain run, and the result, up to that power, is the SAME
+    BITS.  (This half does NOT test stale records: the second run has the first one's magnitudes.)  The second half
+    does: scales INSIDE the window, which reach the kernels -- the first stem launch's result 2^-60 lower than in the run
+    before it on the same contractor; every pair must scale with ITS operand's record of THIS run
+    (tests/test_gpu_exec_history.py has the whole property)."""
     nq, gates = G.STEM_CASES[10]
     tree = G.stem_network(nq, gates, 1000)
     arrays = ca.make_arrays_from_inputs(tree.inputs, tree.size_dict, seed=10, dtype="complex64", rescale=True)
@@ -383,11 +379,20 @@ def test_fp16x2_scales_are_exact_powers_of_two(fuse_whatever_fits):
     shifts = [(-90 if i == 0 else (40 if i % 2 else -40)) for i in range(len(arrays))]
     scaled = [(a * np.float32(2.0**s)).astype("complex64") for a, s in zip(arrays, shifts)]
     got = np.asarray(fn(*scaled))
+    # inside the window: the state x 2^-20, the three gate tensors under the first launch x 2^-13, 2^-13, 2^-14
+    inwin = [G.scaled_in_window(a, {0: -20, 1: -13, 2: -13, 3: -14}.get(i, 0)) for i, a in enumerate(arrays)]
+    small = np.asarray(fn(*inwin))
     fn.close()
     total = sum(shifts)
     assert np.array_equal(got * np.float32(2.0 ** -total) if abs(total) < 120 else got, plain) or \
         G.relerr(got.astype("complex128") * 2.0 ** -total, ref) <= 1e-5
     assert G.relerr(got.astype("complex128") * 2.0 ** -total, ref) <= G.single_gate(ref, orc.contract(tree, arrays))
+    ref_small = np.asarray(orc.contract(tree, [a.astype("complex128") for a in inwin]))
+    assert G.relerr(small, ref_small) <= G.single_gate(ref_small, orc.contract(tree, inwin))
+    f2 = HipContractor(tree, fuse=True, fuse_min_elems=1 << 10)
+    fresh = np.asarray(f2(*inwin))
+    f2.close()
+    assert np.array_equal(small, fresh)
 
 
 def test_fp16x2_wide_dynamic_range_is_norm_wise(fuse_whatever_fits):
@@ -447,17 +452,7 @@ def test_first_pair_of_a_stem_runs_bf16x3_and_records_its_maximum(monkeypatch):
 # ---------------------------------------------------------------------- #
 
 
-def _chain_tree(R, K, N, N2=None):
-    """a[R, K] b[K, N] (c[N, N2]): one long tiled step, or two of them in a chain (the second one's big operand
-    produced -- and its largest element recorded -- by the first)."""
-    if N2 is None:
-        return ca.ContractionTree.from_path([("a", "b"), ("b", "c")], ("a", "c"), dict(a=R, b=K, c=N), path=[(0, 1)])
-    return ca.ContractionTree.from_path([("a", "b"), ("b", "c"), ("c", "d")], ("a", "d"), dict(a=R, b=K, c=N, d=N2),
-                                        path=[(0, 1), (0, 1)])
-
-
-def _cplx(rng, *shape):
-    return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype("complex64")
+_chain_tree, _cplx = G.chain_tree, G.cplx
 
 
 @pytest.mark.parametrize("R,K,N", [(8192, 512, 512), (65536, 64, 64), (32768, 256, 128)])

@@ -149,6 +149,35 @@ def test_vjp_repeated_calls():
     fn.close()
 
 
+def test_vjp_repeated_calls_single_precision():
+    """complex64: two different uploads on one contractor -- the second with every leaf and the cotangent scaled by
+    powers of two inside the upload window [2^-32, 2^32), so that the kernels see them -- against the reference under
+    this file's gate, and the same bits as a contractor that only ever saw that upload."""
+    case = _case("rand_s42_r3_o2_hi2_ho2_sliced")
+    tree = G.tree_of(case)
+    plan = compile_vjp(tree, "complex64")
+    fn = HipContractor(tree)
+    for seed, shifts in ((1, None), (2, (-20, 5, 5)), (1, None)):
+        arrays = ca.make_arrays_from_inputs(tree.inputs, tree.size_dict, seed=seed, dtype="complex128")
+        h = V.cotangent(tree, "complex128", seed=seed)
+        if shifts is not None:
+            arrays = [G.scaled_in_window(a, shifts[i % 3]) for i, a in enumerate(arrays)]
+            h = G.scaled_in_window(h, -12)
+        ref = V.reference_vjp(tree, arrays, h)
+        xs, hx = [a.astype("complex64") for a in arrays], h.astype("complex64")
+        for x in xs + [hx]:
+            G.assert_in_upload_window(x)
+        got = fn.vjp(*xs, cotangent=hx)
+        npy = V.split_grads(plan, run_plan(plan, xs + [hx]), [a.shape for a in xs])
+        fresh_fn = HipContractor(tree)
+        fresh = fresh_fn.vjp(*xs, cotangent=hx)
+        fresh_fn.close()
+        for i, (g, r) in enumerate(zip(got, ref)):
+            assert G.relerr(g, r) <= max(1e-5, 8 * G.relerr(npy[i], r)), (seed, i)
+            assert np.array_equal(g, fresh[i]), (seed, i)
+    fn.close()
+
+
 def test_vjp_slice_batching_bit_identical(monkeypatch):
     case = _case("lattice8x8_sliced")
     outs = []
