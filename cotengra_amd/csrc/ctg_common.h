@@ -518,6 +518,10 @@ struct ValuGroupItem {
 };
 constexpr int64_t kValuGroupMaxTiles = 4096;  // larger steps fill the chip on their own
 bool valu_thread_per_output(const StepArgs& p);  // the route launch_pair_valu takes for this step
+// the kernels launch_pair_valu takes for this step: "pair_valu_kernel" (thread per output), or the k-reduction
+// kernel and its finish pass, "pair_kred_kernel + pair_kred_finish_kernel<WAVE>" (pair_kred_multi_kernel<NO>
+// for two to four outputs)
+void pair_valu_name(int dtype, const StepArgs& p, int64_t scratch_bytes, char* buf, size_t n);
 uint32_t valu_group_fill(const StepArgs& p, ValuGroupItem* it, uint32_t block_begin);  // -> n_blocks
 hipError_t launch_pair_valu_group(int dtype, const ValuGroupItem* d_items, int n_items, uint32_t blocks,
                                   int nz, hipStream_t stream);
@@ -541,8 +545,10 @@ int64_t fast_lane_table_bytes();
 hipError_t launch_fast_lane_consts(const StepArgs& p, const MfmaHints& h, void* out, hipStream_t stream);
 // complex128 on the FP64 matrix cores (ctg_pair_mfma_f64.hip)
 hipError_t launch_pair_mfma_c128(const StepArgs& p, int flags, hipStream_t stream);
+void pair_mfma_c128_name(const StepArgs& p, char* buf, size_t n);   // the instantiation that launch takes
 // float32 / float64 on the 16x16x4 matrix-core instructions
 hipError_t launch_pair_mfma_real(int dtype, const StepArgs& p, int flags, hipStream_t stream);
+void pair_mfma_real_name(int dtype, const StepArgs& p, int flags, char* buf, size_t n);
 // fused stem pair (ctg_stem.hip; kernels and shape rules: ctg_stem_impl.h)
 bool stem2_supported(const StemArgs& p);
 bool stem3_supported(const StemArgs& p);   // (a three-step tile: shape, instantiation, LDS)

@@ -235,60 +235,81 @@ __global__ __launch_bounds__(256) void pair_kred_finish_kernel(StepArgs p, int64
     }
 }
 
+// The route of a step through launch_pair_valu_t, the one place that decides it for the launcher and for the
+// name the executor reports (ctg_exec_step_kernel): few outputs under a long contraction put lanes along k --
+// G partial sums per output over `chunk` k each, added by a finish pass -- everything else is a thread per output.
+struct ValuRoute {
+    bool kred;        // lanes along k: pair_kred_kernel / pair_kred_multi_kernel<multi> + pair_kred_finish_kernel
+    int multi;        // 2-4: that many outputs, one wave per k-chunk computes all of them; 0: a wave per output
+    bool wave_finish; // few outputs, many partials: a wavefront per output adds them
+    int64_t G, chunk;
+};
+
+static ValuRoute valu_route(const StepArgs& p, int64_t elem_bytes, int64_t scratch_bytes) {
+    ValuRoute r{false, 0, false, 0, 0};
+    const int64_t outs = p.R * p.N;
+    // few outputs, long contraction -> lanes along k
+    if (!(p.K >= 256 && outs <= (1 << 15))) return r;
+    // k per work item: long enough to keep the partial-sum traffic low, short
+    // enough that a handful of outputs still spreads over the whole chip
+    // (at most 256 partials per output: the finish pass adds them serially)
+    int64_t per_item = outs <= 64 ? 512 : 2048;
+    if (per_item * 256 < p.K) per_item = (p.K + 255) / 256;
+    int64_t G = (p.K + per_item - 1) / per_item;
+    const int64_t want = (1 << 14) / (outs > 0 ? outs : 1);  // ~16k waves fill the chip
+    if (G > want) G = want;
+    if (G < 1) G = 1;
+    const int64_t cap = scratch_bytes / elem_bytes / (outs > 0 ? outs : 1);
+    if (G > cap) G = cap;
+    if (G < 1) return r;
+    int64_t chunk = (p.K + G - 1) / G;
+    chunk = (chunk + 63) / 64 * 64;
+    r.kred = true;
+    r.chunk = chunk;
+    r.G = (p.K + chunk - 1) / chunk;
+    r.multi = outs >= 2 && outs <= 4 ? (int)outs : 0;
+    r.wave_finish = outs <= 4096 && r.G >= 16;
+    return r;
+}
+
 template <typename T>
 static hipError_t launch_pair_valu_t(const StepArgs& p, void* scratch, int64_t scratch_bytes,
                                      hipStream_t stream) {
     const int64_t outs = p.R * p.N;
-    // few outputs, long contraction -> lanes along k
-    if (p.K >= 256 && outs <= (1 << 15)) {
-
-        // k per work item: long enough to keep the partial-sum traffic low, short
-        // enough that a handful of outputs still spreads over the whole chip
-        // (at most 256 partials per output: the finish pass adds them serially)
-        int64_t per_item = outs <= 64 ? 512 : 2048;
-        if (per_item * 256 < p.K) per_item = (p.K + 255) / 256;
-        int64_t G = (p.K + per_item - 1) / per_item;
-        const int64_t want = (1 << 14) / (outs > 0 ? outs : 1);  // ~16k waves fill the chip
-        if (G > want) G = want;
-        if (G < 1) G = 1;
-        const int64_t cap = scratch_bytes / (int64_t)sizeof(T) / (outs > 0 ? outs : 1);
-        if (G > cap) G = cap;
-        if (G >= 1) {
-            int64_t chunk = (p.K + G - 1) / G;
-            chunk = (chunk + 63) / 64 * 64;
-            G = (p.K + chunk - 1) / chunk;
-            const int64_t items = outs * G;
-            // (G is a function of the step alone; the partial sums of every slice of a
-            // batch must fit the scratch buffer, else the slices go one by one)
-            const int64_t room = p.scratch_total > scratch_bytes ? p.scratch_total : scratch_bytes;
-            if (p.nz > 1 && items * (int64_t)sizeof(T) * p.nz > room)
-                return for_each_z_chunk(p, room / (items * (int64_t)sizeof(T)), [&](const StepArgs& q) {
-                    return launch_pair_valu_t<T>(q, scratch, scratch_bytes, stream);
-                });
-            int64_t blocks = (items + 3) / 4;
-            if (blocks > 8192) blocks = 8192;
-            if (outs >= 2 && outs <= 4) {
-                // (a handful of outputs: every wave takes a k-chunk of all of them)
-                int64_t mb = (G + 3) / 4;
-                if (mb > 8192) mb = 8192;
-                const dim3 mg((unsigned)mb, (unsigned)p.nz);
-                if (outs == 2) hipLaunchKernelGGL((pair_kred_multi_kernel<T, 2>), mg, dim3(256), 0, stream, p, G, chunk, (T*)scratch);
-                else if (outs == 3) hipLaunchKernelGGL((pair_kred_multi_kernel<T, 3>), mg, dim3(256), 0, stream, p, G, chunk, (T*)scratch);
-                else hipLaunchKernelGGL((pair_kred_multi_kernel<T, 4>), mg, dim3(256), 0, stream, p, G, chunk, (T*)scratch);
-            } else
+    const ValuRoute route = valu_route(p, (int64_t)sizeof(T), scratch_bytes);
+    if (route.kred) {
+        const int64_t G = route.G, chunk = route.chunk;
+        const int64_t items = outs * G;
+        // (G is a function of the step alone; the partial sums of every slice of a
+        // batch must fit the scratch buffer, else the slices go one by one)
+        const int64_t room = p.scratch_total > scratch_bytes ? p.scratch_total : scratch_bytes;
+        if (p.nz > 1 && items * (int64_t)sizeof(T) * p.nz > room)
+            return for_each_z_chunk(p, room / (items * (int64_t)sizeof(T)), [&](const StepArgs& q) {
+                return launch_pair_valu_t<T>(q, scratch, scratch_bytes, stream);
+            });
+        int64_t blocks = (items + 3) / 4;
+        if (blocks > 8192) blocks = 8192;
+        if (route.multi) {
+            // (a handful of outputs: every wave takes a k-chunk of all of them)
+            int64_t mb = (G + 3) / 4;
+            if (mb > 8192) mb = 8192;
+            const dim3 mg((unsigned)mb, (unsigned)p.nz);
+            if (route.multi == 2) hipLaunchKernelGGL((pair_kred_multi_kernel<T, 2>), mg, dim3(256), 0, stream, p, G, chunk, (T*)scratch);
+            else if (route.multi == 3) hipLaunchKernelGGL((pair_kred_multi_kernel<T, 3>), mg, dim3(256), 0, stream, p, G, chunk, (T*)scratch);
+            else hipLaunchKernelGGL((pair_kred_multi_kernel<T, 4>), mg, dim3(256), 0, stream, p, G, chunk, (T*)scratch);
+        } else
             hipLaunchKernelGGL(pair_kred_kernel<T>, dim3((unsigned)blocks, (unsigned)p.nz), dim3(256), 0, stream, p,
                                G, chunk, (T*)scratch);
-            if (outs <= 4096 && G >= 16) {
-                hipLaunchKernelGGL((pair_kred_finish_kernel<T, true>), dim3((unsigned)((outs + 3) / 4), (unsigned)p.nz),
-                                   dim3(256), 0, stream, p, G, (const T*)scratch);
-            } else {
-                int64_t fblocks = (outs + 255) / 256;
-                if (fblocks > 4096) fblocks = 4096;
-                hipLaunchKernelGGL((pair_kred_finish_kernel<T, false>), dim3((unsigned)fblocks, (unsigned)p.nz),
-                                   dim3(256), 0, stream, p, G, (const T*)scratch);
-            }
-            return hipGetLastError();
+        if (route.wave_finish) {
+            hipLaunchKernelGGL((pair_kred_finish_kernel<T, true>), dim3((unsigned)((outs + 3) / 4), (unsigned)p.nz),
+                               dim3(256), 0, stream, p, G, (const T*)scratch);
+        } else {
+            int64_t fblocks = (outs + 255) / 256;
+            if (fblocks > 4096) fblocks = 4096;
+            hipLaunchKernelGGL((pair_kred_finish_kernel<T, false>), dim3((unsigned)fblocks, (unsigned)p.nz),
+                               dim3(256), 0, stream, p, G, (const T*)scratch);
         }
+        return hipGetLastError();
     }
     ValuGroupItem it;
     valu_group_fill(p, &it, 0);
@@ -338,6 +359,15 @@ hipError_t launch_pair_valu(int dtype, const StepArgs& p, void* scratch, int64_t
         case 3: return launch_pair_valu_t<c128>(p, scratch, scratch_bytes, stream);
     }
     return hipErrorInvalidValue;
+}
+
+void pair_valu_name(int dtype, const StepArgs& p, int64_t scratch_bytes, char* buf, size_t n) {
+    static const int64_t elem_bytes[4] = {sizeof(float), sizeof(double), sizeof(c64), sizeof(c128)};
+    const ValuRoute r = valu_route(p, elem_bytes[dtype & 3], scratch_bytes);
+    const char* fin = r.wave_finish ? "true" : "false";
+    if (!r.kred) snprintf(buf, n, "pair_valu_kernel");
+    else if (r.multi) snprintf(buf, n, "pair_kred_multi_kernel<%d> + pair_kred_finish_kernel<%s>", r.multi, fin);
+    else snprintf(buf, n, "pair_kred_kernel + pair_kred_finish_kernel<%s>", fin);
 }
 
 // ------------------------------------------------------------------------- //

@@ -14,6 +14,7 @@
 // row offsets and the k offsets of the next steps resolved into LDS.
 #include "ctg_common.h"
 
+#include <cstdio>
 #include <type_traits>
 
 namespace ctg {
@@ -254,12 +255,20 @@ static hipError_t launch_c128_t(const StepArgs& p, int flags, hipStream_t stream
     return hipGetLastError();
 }
 
+// The tile of a step: the tall one once its blocks alone fill the chip twice over.  The one place
+// that decides it, for the launcher and for the name the executor reports (ctg_exec_step_kernel).
+static bool c128_tall(const StepArgs& p) {
+    return ((p.R + 127) / 128) * ((p.N + 31) / 32) * p.Bt >= 1024;
+}
+
 // flags: bit0 = A's fastest-varying memory index is a contracted one, bit1 = same for B
 hipError_t launch_pair_mfma_c128(const StepArgs& p, int flags, hipStream_t stream) {
-    // the tall tile once its blocks alone fill the chip twice over
-    const int64_t tall = ((p.R + 127) / 128) * ((p.N + 31) / 32) * p.Bt;
-    if (tall >= 1024) return launch_c128_t<4, 2>(p, flags, stream);
+    if (c128_tall(p)) return launch_c128_t<4, 2>(p, flags, stream);
     return launch_c128_t<2, 2>(p, flags, stream);
+}
+
+void pair_mfma_c128_name(const StepArgs& p, char* buf, size_t n) {
+    snprintf(buf, n, "pair_mfma_c128_kernel<%d,2>", c128_tall(p) ? 4 : 2);
 }
 
 }  // namespace ctg
@@ -588,16 +597,29 @@ __global__ __launch_bounds__(256, 2) void pair_mfma_real_kernel(StepArgs p, int 
     }
 }
 
+// Both operands gather in 16-byte pieces (flags bit 2 / bit 3: the host's real_vec_ok of A / B).
+static bool real_vec(int flags) { return (flags & 4) && (flags & 8); }
+
+// The tile of a step, as 10 * TM + TN: the large one once its blocks alone fill the chip twice
+// over.  With real_vec the one place that decides the instantiation, for the launcher and for
+// the name the executor reports (ctg_exec_step_kernel).
+static int real_tile(int dtype, const StepArgs& p) {
+    const int64_t big = ((p.R + 127) / 128) * ((p.N + 127) / 128) * p.Bt;
+    const int64_t tall = ((p.R + 127) / 128) * ((p.N + 63) / 64) * p.Bt;
+    // (128 x 128 in double precision would need more than 256 registers per lane)
+    if (dtype == 0 && big >= 1024 && p.N >= 96) return 44;
+    return tall >= 1024 ? 42 : 22;
+}
+
 template <typename T, int TM, int TN>
 static hipError_t launch_real_t(const StepArgs& p, int flags, hipStream_t stream) {
-    const bool vec = (flags & 4) && (flags & 8);   // both operands gather in 16-byte pieces
     constexpr int RBM = 2 * TM * 16, RBN = 2 * TN * 16;
     const int64_t tiles_m = (p.R + RBM - 1) / RBM;
     const int64_t tiles_n = (p.N + RBN - 1) / RBN;
     const int64_t gx = ((tiles_m + 7) / 8) * 8 * tiles_n;
     if (gx > 0x7fffffffll || p.Bt > 65535 || p.nz > 65535) return hipErrorInvalidValue;
     const dim3 grid((unsigned)gx, (unsigned)p.nz, (unsigned)p.Bt);
-    if (vec)
+    if (real_vec(flags))
         hipLaunchKernelGGL((pair_mfma_real_kernel<T, TM, TN, true>), grid, dim3(256), 0, stream, p, flags,
                            tiles_m, tiles_n);
     else
@@ -608,18 +630,20 @@ static hipError_t launch_real_t(const StepArgs& p, int flags, hipStream_t stream
 
 hipError_t launch_pair_mfma_real(int dtype, const StepArgs& p, int flags, hipStream_t stream) {
     if (dtype != 0 && dtype != 1) return hipErrorInvalidValue;
-    // the large tile once its blocks alone fill the chip twice over
-    const int64_t big = ((p.R + 127) / 128) * ((p.N + 127) / 128) * p.Bt;
-    const bool wide = big >= 1024 && p.N >= 96;
-    const int64_t tall = ((p.R + 127) / 128) * ((p.N + 63) / 64) * p.Bt;
+    const int tile = real_tile(dtype, p);
     if (dtype == 0) {
-        if (wide) return launch_real_t<float, 4, 4>(p, flags, stream);
-        if (tall >= 1024) return launch_real_t<float, 4, 2>(p, flags, stream);
+        if (tile == 44) return launch_real_t<float, 4, 4>(p, flags, stream);
+        if (tile == 42) return launch_real_t<float, 4, 2>(p, flags, stream);
         return launch_real_t<float, 2, 2>(p, flags, stream);
     }
-    // (128 x 128 in double precision would need more than 256 registers per lane)
-    if (tall >= 1024) return launch_real_t<double, 4, 2>(p, flags, stream);
+    if (tile == 42) return launch_real_t<double, 4, 2>(p, flags, stream);
     return launch_real_t<double, 2, 2>(p, flags, stream);
+}
+
+void pair_mfma_real_name(int dtype, const StepArgs& p, int flags, char* buf, size_t n) {
+    const int tile = real_tile(dtype, p);
+    snprintf(buf, n, "pair_mfma_real_kernel<%s,%d,%d,%s>", dtype == 0 ? "float" : "double", tile / 10, tile % 10,
+             real_vec(flags) ? "true" : "false");
 }
 
 }  // namespace ctg

@@ -2527,9 +2527,10 @@ int ctg_exec_step_kernel(ctg_exec* e, int64_t step, char* buf, int64_t buflen) {
         if (stem_step_h2(e, step, prod16)) stem2h_kernel_name(e->stem_args[step], name, sizeof(name));
         else stem2_kernel_name(e->stem_args[step], name, sizeof(name));
     } else if (r[W_KERNEL] == KERNEL_MFMA && p->dtype == CTG_C128) {
-        snprintf(name, sizeof(name), "pair_mfma_c128_kernel");
+        // (tile and gather width: asked of the launcher's own rules, for the launch of one slice)
+        pair_mfma_c128_name(e->args[step], name, sizeof(name));
     } else if (r[W_KERNEL] == KERNEL_MFMA && p->dtype != CTG_C64) {
-        snprintf(name, sizeof(name), "pair_mfma_real_kernel<%s>", p->dtype == CTG_F32 ? "float" : "double");
+        pair_mfma_real_name(p->dtype, e->args[step], e->hints[step].vecA, name, sizeof(name));
     } else if (r[W_KERNEL] == KERNEL_MFMA) {
         const MfmaHints& h = e->hints[step];
         if (h.stream == 4)
@@ -2554,7 +2555,7 @@ int ctg_exec_step_kernel(ctg_exec* e, int64_t step, char* buf, int64_t buflen) {
                      h.fast ? "pair_mfma_fast_kernel" : "pair_mfma_c64_kernel", h.bn,
                      h.vecA ? "true" : "false");
     } else {
-        snprintf(name, sizeof(name), "pair_valu_kernel");
+        pair_valu_name(p->dtype, e->args[step], kScratchBytes, name, sizeof(name));
     }
     snprintf(buf, (size_t)buflen, "%s", name);
     return CTG_OK;

@@ -278,7 +278,18 @@ int ctg_exec_profile_slice(ctg_exec* exec, int64_t slice_id, float* ms);
 
 /* Name of the kernel that executes plan step `step` on this executor (e.g.
  * "pair_mfma_fast_kernel<128,128,16>"), NUL-terminated into `buf`; lets a
- * profile attribute per-step timings to rocprof kernel names. */
+ * profile attribute per-step timings to rocprof kernel names.  The name is the
+ * profiler's, shortened: no namespace, no argument list, template arguments as the
+ * launcher chose them for a launch of one slice.  Pair steps in float32, float64
+ * and complex128 spell out tile and gather width:
+ *   "pair_mfma_c128_kernel<TM,TN>"                           e.g. <4,2>
+ *   "pair_mfma_real_kernel<float|double,TM,TN,true|false>"   (last: 16-byte gathers)
+ * and the steps of every type that do not run on the matrix cores are
+ *   "pair_valu_kernel"                                       a thread per output
+ *   "pair_kred_kernel + pair_kred_finish_kernel<true|false>" lanes along a long k
+ *   "pair_kred_multi_kernel<2|3|4> + pair_kred_finish_kernel<true|false>"
+ * (two launches: the partial sums and the pass that adds them, a wavefront per
+ * output when <true>).  Match by prefix. */
 int ctg_exec_step_kernel(ctg_exec* exec, int64_t step, char* buf, int64_t buflen);
 
 int ctg_exec_sync(ctg_exec* exec);

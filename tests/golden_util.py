@@ -108,6 +108,40 @@ def stem_flags(name):
             "ws": t[16] if len(t) > 16 else False}   # (specialised waves)
 
 
+def pair_flags(name):
+    """What the executor says of a pair step in float32, float64 or complex128, or of a step of any type that does
+    not run on the matrix cores (include/ctg_hip.h: ctg_exec_step_kernel): ``kernel``, the name without template
+    arguments, and -- matrix-core kernels -- ``dtype`` ("float", "double" or "c128"), the MFMA tiles per wave
+    ``tm``, ``tn`` and ``vec``, the 16-byte gathers (None in complex128); -- long contractions -- ``no``, the
+    outputs a wave computes together (0: pair_kred_kernel, a wave per output), and ``finish_wave``, whether a
+    wavefront per output adds the partial sums."""
+    parts = [x.strip() for x in name.split(" + ")]
+
+    def args(s):
+        return [x.strip() for x in s[s.index("<") + 1 : s.rindex(">")].split(",")] if "<" in s else []
+
+    head = parts[0]
+    out = {"kernel": head.split("<")[0], "dtype": None, "tm": 0, "tn": 0, "vec": None, "no": 0, "finish_wave": None}
+    a = args(head)
+    if out["kernel"] == "pair_mfma_c128_kernel":
+        out.update(dtype="c128", tm=int(a[0]), tn=int(a[1]))
+    elif out["kernel"] == "pair_mfma_real_kernel":
+        assert a[0] in ("float", "double") and a[3] in ("true", "false"), name
+        out.update(dtype=a[0], tm=int(a[1]), tn=int(a[2]), vec=a[3] == "true")
+    elif out["kernel"] == "pair_kred_multi_kernel":
+        out["no"] = int(a[0])
+    else:
+        assert out["kernel"] in ("pair_valu_kernel", "pair_kred_kernel") and not a, name
+    if out["kernel"].startswith("pair_kred"):
+        assert len(parts) == 2 and parts[1].startswith("pair_kred_finish_kernel<"), name
+        (w,) = args(parts[1])
+        assert w in ("true", "false"), name
+        out["finish_wave"] = w == "true"
+    else:
+        assert len(parts) == 1, name
+    return out
+
+
 def stem_network(nq, gates, seed, sliced=0):
     """A small 'stem': one tensor of ``nq`` binary indices to which tensors are
     applied one after the other, gate ``(k, n)`` contracting ``k`` randomly chosen

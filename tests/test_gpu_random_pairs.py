@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import cotengra_amd as ca
+import golden_util as G
 from cotengra_amd.interface import einsum
 
 pytestmark = pytest.mark.gpu
@@ -93,3 +94,33 @@ def test_random_pair(idx):
     scale = max(np.abs(ref).max(), 1e-300)
     tol = 5e-4 if dtype in ("complex64", "float32") else 1e-11
     assert np.abs(got - ref).max() <= tol * scale, (eq, size, dtype)
+
+
+# test_random_pair takes dtype and shape style from nearly the same counter modulo 6: complex128 never meets the
+# styles 0-2 there, float32 never 1-3, float64 never 2-4.  Here: ten cases of every style in each of the three.
+OTHER = [(s, random_case(s)) for s in range(60)]
+
+
+@pytest.mark.parametrize("dtype", ["complex128", "float32", "float64"])
+@pytest.mark.parametrize("seed", [s for s, c in OTHER if c is not None])
+def test_random_pair_other_dtypes(seed, dtype):
+    eq, size = OTHER[seed][1]
+    (ta, tb), _ = ca.eq_to_inputs_output(eq)
+    rng = np.random.default_rng(5000 + seed)
+
+    def mk(t):
+        shape = [size[i] for i in t]
+        x = rng.normal(size=shape)
+        if "complex" in dtype:
+            x = x + 1j * rng.normal(size=shape)
+        return x.astype(dtype)
+
+    a, b = mk(ta), mk(tb)
+    hi = "complex128" if "complex" in dtype else "float64"
+    ref = np.einsum(eq, a.astype(hi), b.astype(hi), optimize=True)
+    got = np.asarray(einsum(eq, a, b, optimize=[(0, 1)]))
+    assert got.shape == ref.shape
+    # float32: the suite's rule for single precision, never above the flat 5e-4 of test_random_pair
+    tol = min(G.single_gate(ref, np.einsum(eq, a, b, optimize=True)), 5e-4) if dtype == "float32" else 1e-11
+    err = G.relerr(got, ref)
+    assert err <= tol, (eq, size, dtype, err, tol)

@@ -292,30 +292,42 @@ def test_plain_c_driver_of_the_collective(tmp_path):
 
 
 # ---------------------------------------------------------------------- #
-# float32 / float64 matrix-core kernel: 16-byte gathers where the layout allows
+# float32 / float64 steps below and at the planner's threshold for the matrix cores (plan.choose_kernel: M N >=
+# 2^16).  Seven of these eight cases are below it: six run on the thread-per-output kernel, pair_valu_kernel, one
+# on the k-reduction kernel; the last one reaches pair_mfma_real_kernel.  The 16-byte gathers of that kernel, which this test is named after and was
+# written for before the threshold moved, are covered by tests/test_gpu_pair_variants.py.
 # ---------------------------------------------------------------------- #
 
 REAL_CASES = [
-    ("ab,bc->ac", dict(a=256, b=128, c=192)),     # A along k, B along its columns: both in pieces
-    ("ab,cb->ac", dict(a=256, b=128, c=192)),     # B along k
-    ("ba,bc->ac", dict(a=256, b=128, c=192)),     # A along its rows
-    ("ba,cb->ca", dict(a=192, b=256, c=128)),     # rows of A fastest, k of B fastest, output transposed
-    ("ab,bc->ac", dict(a=130, b=66, c=70)),       # extents that are multiples of 2 only: double yes, float no
-    ("ab,bc->ac", dict(a=129, b=65, c=67)),       # odd extents: element-wise path
-    ("xab,xbc->xac", dict(x=3, a=128, b=64, c=64)),   # batch index
-    ("abk,kcd->abcd", dict(a=32, b=16, k=64, c=8, d=16)),   # fused index groups
+    # (equation, extents, the kernel of the step)
+    ("ab,bc->ac", dict(a=256, b=128, c=192), "pair_valu_kernel"),     # A along k, B along its columns
+    ("ab,cb->ac", dict(a=256, b=128, c=192), "pair_valu_kernel"),     # B along k
+    ("ba,bc->ac", dict(a=256, b=128, c=192), "pair_valu_kernel"),     # A along its rows
+    # rows of A fastest, k of B fastest, output transposed; K = 256 under 2^15 outputs: lanes along k
+    ("ba,cb->ca", dict(a=192, b=256, c=128), "pair_kred_kernel"),
+    ("ab,bc->ac", dict(a=130, b=66, c=70), "pair_valu_kernel"),       # extents that are multiples of 2 only
+    ("ab,bc->ac", dict(a=129, b=65, c=67), "pair_valu_kernel"),       # odd extents
+    ("xab,xbc->xac", dict(x=3, a=128, b=64, c=64), "pair_valu_kernel"),   # batch index
+    ("abk,kcd->abcd", dict(a=32, b=16, k=64, c=8, d=16), "pair_mfma_real_kernel"),   # fused index groups: 512 x 128
 ]
 
 
 @pytest.mark.parametrize("dtype", ["float32", "float64"])
 @pytest.mark.parametrize("case", range(len(REAL_CASES)))
 def test_real_kernel_vector_gathers(case, dtype):
+    """Real-valued GEMM-like steps against numpy in float64, whole and with the contracted index sliced (an outer
+    product per slice, on pair_valu_kernel).  The kernel of the unsliced step is asserted, so that the test cannot
+    drift off it unnoticed."""
     from cotengra_amd.interface import einsum
 
-    eq, sizes = REAL_CASES[case]
+    eq, sizes, kernel = REAL_CASES[case]
     (ta, tb), out = ca.eq_to_inputs_output(eq)
     rng = np.random.default_rng(case)
     a, b = (rng.normal(size=[sizes[i] for i in t]).astype(dtype) for t in (ta, tb))
+    fn = HipContractor(ca.ContractionTree.from_path([ta, tb], out, sizes, path=[(0, 1)]))
+    names = [n for n in fn.setup(a, b)["exec"].step_kernels() if n.startswith("pair_")]
+    fn.close()
+    assert len(names) == 1 and G.pair_flags(names[0])["kernel"] == kernel, names
     ref = np.einsum(eq, a.astype("float64"), b.astype("float64"), optimize=True)
     got = np.asarray(einsum(eq, a, b, optimize=[(0, 1)]))
     assert got.shape == ref.shape and got.dtype == np.dtype(dtype)
