@@ -164,10 +164,6 @@ __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
     return r;
 }
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ unsigned pack_f16(float a, float b) {
-    const _Float16 ha = (_Float16)a, hb = (_Float16)b;
-    return (unsigned)__builtin_bit_cast(unsigned short, ha) | ((unsigned)__builtin_bit_cast(unsigned short, hb) << 16);
-}
 
 // ---- the two arithmetics of the 16-bit matrix cores -----------------------------------------------------------------
 // (limb vectors are carried as bf16x8 in both: 16 bytes of a fragment, whatever the format of its halves)
@@ -239,17 +235,39 @@ struct Fp16x2 {
     static constexpr const char* kernel_name = "stem2h_kernel";
     __device__ __forceinline__ static constexpr int t_step(int t) { return t == 1 ? 2 : (t == 3 ? 3 : 1); }
     __device__ __forceinline__ static constexpr int t_index(int t) { return t == 3 ? 2 : t; }
-    // x * scale as two rounded fp16 limbs (v_cvt_pk_f16_f32 rounds to nearest even and packs two values; the
-    // residual x s - h1 is exact in fp32); o[2] is not used by any product.  4 vector instructions per value.
+    // x * scale as two rounded fp16 limbs, h1 = rn16(x s) and h2 = rn16(x s - h1); o[2] is not used by any product.
+    // TWO vector instructions per value, none to pack: v_fma_mixlo_f16 / v_fma_mixhi_f16 compute an fp32 fma, round it to
+    // fp16 (nearest even) and write the low / the high half of the destination, leaving the other half alone -- a pair
+    // of values lands packed in the word the MFMA reads -- and they take the first limb as an fp16 source, so the
+    // residual needs no conversion back (x s is exact for a power of two s, and so is the fp32 residual: the fma rounds
+    // once, to fp16).  The compiler selects the mixlo form for the scalar C++ of this arithmetic but never the mixhi one:
+    // it shifted and or-ed the halves together, 4 instructions per value (profiles/stem_valu_diet.txt).  The addend 0 of
+    // the first limb is the compiler's own form of the product.
+    // What the assembler does not pad, inside the strings: one state between mixhi's half-register write and the mixlo
+    // that reads that register, and two between the last limb written and the MFMA that takes it (the closing statement,
+    // which every limb word passes through).  scale is wave-uniform (a power of two from kernel arguments or from the
+    // tile's maximum record): a scalar operand.
+    // A CALLER'S SIDE of the same: x[] must come from a load (global or LDS, as at all six call sites), never straight
+    // from an MFMA's destination, and o[] must not be the C or D of an MFMA in flight -- the compiler pads no
+    // MFMA-to-VALU wait states around an asm statement, a split of accumulators would read them stale, silently.
+    // (store_limbs below stays scalar C++: single 16-bit values written once per launch, nothing to pack.)
     __device__ __forceinline__ static void split(const float (&x)[8], bf16x8 (&o)[3], float scale = 1.f) {
         u32x4 p1, p2;
+        const float s = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, scale)));
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float a = x[2 * i] * scale, b = x[2 * i + 1] * scale;
-            const _Float16 ha = (_Float16)a, hb = (_Float16)b;
-            p1[i] = (unsigned)__builtin_bit_cast(unsigned short, ha) | ((unsigned)__builtin_bit_cast(unsigned short, hb) << 16);
-            p2[i] = pack_f16(a - (float)ha, b - (float)hb);
+            unsigned h1, h2;
+            asm("v_fma_mixlo_f16 %0, %2, %4, 0\n\t"
+                "v_fma_mixhi_f16 %0, %3, %4, 0\n\t"
+                "s_nop 0\n\t"
+                "v_fma_mixlo_f16 %1, %2, %4, -%0 op_sel_hi:[0,0,1]\n\t"
+                "v_fma_mixhi_f16 %1, %3, %4, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
+                : "=&v"(h1), "=&v"(h2)
+                : "v"(x[2 * i]), "v"(x[2 * i + 1]), "s"(s));
+            p1[i] = h1;
+            p2[i] = h2;
         }
+        asm("s_nop 1" : "+v"(p1), "+v"(p2));
         o[0] = __builtin_bit_cast(bf16x8, p1);
         o[1] = __builtin_bit_cast(bf16x8, p2);
         o[2] = o[1];
