@@ -541,6 +541,10 @@ uint32_t fast_group_fill(const StepArgs& p, const MfmaHints& h, FastGroupItem* i
 hipError_t launch_pair_mfma_fast_group(int key, const FastGroupItem* d_items, int n_items, uint32_t blocks,
                                        int nz, hipStream_t stream);
 bool rowwise_ok(const StepArgs& p);  // shapes the row-wise kernel takes (MfmaHints::stream == 4)
+// the kernels that launch takes for a complex64 step, with their template arguments: "pair_mfma_stream_kernel<FN,VEC,ADD,
+// SHORTK,NV>", "pair_rowwise_kernel<NN,TS>", "pair_skinny_kernel<K,N>", "pair_mfma_kstream_kernel<FN,VEC>", or a tiled
+// kernel, "pair_mfma_{c64,fast,bf3,h2}_kernel<128,BN,16>,VEC"; where slabs are reduced, " + splitk_reduce_kernel[S]"
+void pair_mfma_c64_name(const StepArgs& p, const MfmaHints& h, int64_t scratch_bytes, char* buf, size_t n);
 int64_t fast_lane_table_bytes();
 hipError_t launch_fast_lane_consts(const StepArgs& p, const MfmaHints& h, void* out, hipStream_t stream);
 // complex128 on the FP64 matrix cores (ctg_pair_mfma_f64.hip)

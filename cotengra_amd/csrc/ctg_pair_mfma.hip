@@ -1269,17 +1269,41 @@ bool pair_bf16x3_on(const StepArgs& p) {
     return p.bf3 != 0;
 }
 
+// The instantiation of a tiled step (MfmaHints::stream == 0): kernel, column tile, 16-byte gathers and the number
+// of k-splits (> 1: splitk_reduce_kernel adds the slabs).  The one place that decides it, for the launcher and for
+// the name the executor reports (ctg_exec_step_kernel).
+enum TiledKernel { TILED_C64, TILED_FAST, TILED_BF3, TILED_H2 };
+struct TiledVariant {
+    TiledKernel kernel;
+    int bn;
+    bool vec;
+    int64_t splits;
+};
+static TiledVariant tiled_variant(const StepArgs& p, const MfmaHints& h, int64_t scratch_bytes) {
+    TiledVariant v;
+    // fp32 products as six bf16 products (pair_mfma_bf3_kernel): long contractions on full 64-column tiles
+    // (h.h2: this launch in the fp16 x 2 arithmetic -- the executor's decision, ctg_runtime.hip)
+    if (h.bn == 64 && h.fast && h.bf3 && pair_bf16x3_on(p)) v.kernel = h.h2 ? TILED_H2 : TILED_BF3;
+    else v.kernel = h.fast ? TILED_FAST : TILED_C64;
+    v.bn = h.bn;
+    v.vec = h.vecA != 0;
+    // split-K when the output alone cannot fill the chip but K is long: decided once per
+    // step when the executor is built (MfmaHints::splitk)
+    const int64_t nk_total = (p.K + MFMA_BK - 1) / MFMA_BK;
+    v.splits = h.splitk > 0 ? h.splitk : mfma_split_count(p.R, p.N, p.K, p.Bt, h.bn, scratch_bytes);
+    if (v.splits > nk_total) v.splits = nk_total;
+    return v;
+}
+
 template <typename Cfg>
 static hipError_t launch_cfg(const StepArgs& p, const MfmaHints& h, void* scratch,
                              int64_t scratch_bytes, hipStream_t stream) {
-    constexpr int BM = Cfg::BM, BN = Cfg::BN, BK = Cfg::BK;
+    constexpr int BM = Cfg::BM, BN = Cfg::BN;
+    static_assert(Cfg::BK == MFMA_BK, "tiled_variant counts k-steps of MFMA_BK");
     const int64_t tiles_m = (p.R + BM - 1) / BM;
     const int64_t tiles_n = (p.N + BN - 1) / BN;
-    // split-K when the output alone cannot fill the chip but K is long: decided once per
-    // step when the executor is built (MfmaHints::splitk)
-    const int64_t nk_total = (p.K + BK - 1) / BK;
-    int64_t S = h.splitk > 0 ? h.splitk : mfma_split_count(p.R, p.N, p.K, p.Bt, BN, scratch_bytes);
-    if (S > nk_total) S = nk_total;
+    const TiledVariant v = tiled_variant(p, h, scratch_bytes);   // (h.bn == BN: launch_pair_mfma)
+    const int64_t S = v.splits;
     if (S > 1 && S * (tiles_m * BM * tiles_n * BN * 8 * p.Bt) > scratch_bytes) return hipErrorInvalidValue;
     // (the split depends on the step alone, never on how many slices a launch
     // carries: a result must not depend on the batching of a run)
@@ -1297,25 +1321,23 @@ static hipError_t launch_cfg(const StepArgs& p, const MfmaHints& h, void* scratc
     const dim3 grid((unsigned)gx, (unsigned)p.nz, (unsigned)p.Bt);
     float* part = S > 1 ? (float*)scratch : (float*)nullptr;
     if constexpr (Cfg::BN == 64) {
-        // fp32 products as six bf16 products (pair_mfma_bf3_kernel): long contractions on full 64-column tiles
-        if (h.fast && h.bf3 && pair_bf16x3_on(p)) {
-            // (h.h2: this launch in the fp16 x 2 arithmetic -- the executor's decision, ctg_runtime.hip; never with
-            // k-splits: the slabs hold unscaled sums)
-            if (h.h2 && S > 1) return hipErrorInvalidValue;
-            const bool h2 = h.h2 != 0;
+        if (v.kernel == TILED_BF3 || v.kernel == TILED_H2) {
+            // (fp16 x 2 never with k-splits: the slabs hold unscaled sums)
+            const bool h2 = v.kernel == TILED_H2;
+            if (h2 && S > 1) return hipErrorInvalidValue;
             const size_t smem = 2 * 2 * (h2 ? 4 : 6) * (size_t)(2 * (Cfg::BM * 8 + CTG_PAIR16_KBPAD) + 2 * (Cfg::BN * 8 + CTG_PAIR16_KBPAD));
             static unsigned long long ready[4] = {0, 0, 0, 0};   // (per-device bit masks, updated atomically: lds_opt_in)
-            const void* fn = h2 ? (h.vecA ? (const void*)pair_mfma_h2_kernel<Cfg, true> : (const void*)pair_mfma_h2_kernel<Cfg, false>)
-                                : (h.vecA ? (const void*)pair_mfma_bf3_kernel<Cfg, true> : (const void*)pair_mfma_bf3_kernel<Cfg, false>);
+            const void* fn = h2 ? (v.vec ? (const void*)pair_mfma_h2_kernel<Cfg, true> : (const void*)pair_mfma_h2_kernel<Cfg, false>)
+                                : (v.vec ? (const void*)pair_mfma_bf3_kernel<Cfg, true> : (const void*)pair_mfma_bf3_kernel<Cfg, false>);
             {
-                const hipError_t e = lds_opt_in(fn, (int)smem, &ready[(h2 ? 2 : 0) + (h.vecA ? 1 : 0)]);
+                const hipError_t e = lds_opt_in(fn, (int)smem, &ready[(h2 ? 2 : 0) + (v.vec ? 1 : 0)]);
                 if (e != hipSuccess) return e;
             }
-            if (h2 && h.vecA)
+            if (h2 && v.vec)
                 hipLaunchKernelGGL((pair_mfma_h2_kernel<Cfg, true>), grid, dim3(256), smem, stream, p, h, tiles_m, tiles_n, k_chunk, part);
             else if (h2)
                 hipLaunchKernelGGL((pair_mfma_h2_kernel<Cfg, false>), grid, dim3(256), smem, stream, p, h, tiles_m, tiles_n, k_chunk, part);
-            else if (h.vecA)
+            else if (v.vec)
                 hipLaunchKernelGGL((pair_mfma_bf3_kernel<Cfg, true>), grid, dim3(256), smem, stream, p, h, tiles_m, tiles_n, k_chunk, part);
             else
                 hipLaunchKernelGGL((pair_mfma_bf3_kernel<Cfg, false>), grid, dim3(256), smem, stream, p, h, tiles_m, tiles_n, k_chunk, part);
@@ -1328,8 +1350,8 @@ static hipError_t launch_cfg(const StepArgs& p, const MfmaHints& h, void* scratc
             return hipGetLastError();
         }
     }
-    if (h.fast) {
-        if (h.vecA)
+    if (v.kernel != TILED_C64) {   // (TILED_FAST: the 16-bit kernels exist on 64 columns only and returned above)
+        if (v.vec)
             hipLaunchKernelGGL((pair_mfma_fast_kernel<Cfg, true>), grid, dim3(256), 0, stream, p, h,
                                tiles_m, tiles_n, k_chunk, part, (const FastGroupItem*)nullptr, 0);
         else
@@ -1337,7 +1359,7 @@ static hipError_t launch_cfg(const StepArgs& p, const MfmaHints& h, void* scratc
                                tiles_m, tiles_n, k_chunk, part, (const FastGroupItem*)nullptr, 0);
     } else if constexpr (Cfg::BN >= 128) {
         return hipErrorInvalidValue;  // the 128-wide tile exists for the fast path only
-    } else if (h.vecA)
+    } else if (v.vec)
         hipLaunchKernelGGL((pair_mfma_c64_kernel<Cfg, true>), grid, dim3(256), 0, stream, p, h,
                            tiles_m, tiles_n, k_chunk, part);
     else
@@ -1852,26 +1874,45 @@ static hipError_t launch_stream_t(const StepArgs& p, const MfmaHints& h, int KP,
     return hipGetLastError();
 }
 
+// The instantiation of a streaming step (MfmaHints::stream == 1), pair_mfma_stream_kernel<FN,VEC,ADD,SHORTK,NV>: the
+// one place that decides it, for the launcher and for the name the executor reports (ctg_exec_step_kernel).
+struct StreamVariant {
+    int fn;        // 16-column fragments of the result: 1, 2, 4
+    bool vec;      // 16-byte gathers of A (only with additive rows)
+    bool add;      // the 32 rows of a group are base + constant
+    bool shortk;   // a contraction shorter than one MFMA k-step: the order table holds only the real columns, 32 K of
+    int nv;        // them per task = the first K / 2 slots of every lane, NV = 2, 4 or 8 of them
+};
+static StreamVariant stream_variant(const StepArgs& p, const MfmaHints& h) {
+    StreamVariant v;
+    v.fn = h.bn / 16;
+    v.add = h.additive32 != 0;
+    v.vec = h.vecA && v.add;
+    v.shortk = p.K < MFMA_BK;
+    v.nv = p.K <= 4 ? 2 : (p.K <= 8 ? 4 : 8);
+    return v;
+}
+
 template <int FN, bool SHORTK, int NV>
-static hipError_t launch_stream_v(const StepArgs& p, const MfmaHints& h, int KP, size_t smem,
+static hipError_t launch_stream_v(const StepArgs& p, const MfmaHints& h, const StreamVariant& v, int KP, size_t smem,
                                   hipStream_t stream) {
-    if (h.vecA && h.additive32) return launch_stream_t<FN, true, true, SHORTK, NV>(p, h, KP, smem, stream);
-    if (h.additive32) return launch_stream_t<FN, false, true, SHORTK, NV>(p, h, KP, smem, stream);
+    if (v.vec) return launch_stream_t<FN, true, true, SHORTK, NV>(p, h, KP, smem, stream);
+    if (v.add) return launch_stream_t<FN, false, true, SHORTK, NV>(p, h, KP, smem, stream);
     return launch_stream_t<FN, false, false, SHORTK, NV>(p, h, KP, smem, stream);
 }
 
 template <int FN>
-static hipError_t launch_stream(const StepArgs& p, const MfmaHints& h, hipStream_t stream) {
+static hipError_t launch_stream(const StepArgs& p, const MfmaHints& h, const StreamVariant& v, hipStream_t stream) {
     const int KP = (int)((p.K + MFMA_BK - 1) / MFMA_BK) * MFMA_BK;
     const int LDB = KP + 4;
     const size_t smem = (size_t)2 * 2 * 16 * FN * LDB * 4 + (size_t)KP * 8 +
                         (size_t)4 * 2 * 32 * (MFMA_BK + 4) * 4;
-    // short contraction: the order table holds only the real columns, 32 K of
-    // them per task = the first K / 2 slots of every lane
-    if (p.K <= 4) return launch_stream_v<FN, true, 2>(p, h, KP, smem, stream);
-    if (p.K <= 8) return launch_stream_v<FN, true, 4>(p, h, KP, smem, stream);
-    if (p.K < MFMA_BK) return launch_stream_v<FN, true, 8>(p, h, KP, smem, stream);
-    return launch_stream_v<FN, false, 8>(p, h, KP, smem, stream);
+    if (!v.shortk) return launch_stream_v<FN, false, 8>(p, h, v, KP, smem, stream);
+    switch (v.nv) {
+        case 2: return launch_stream_v<FN, true, 2>(p, h, v, KP, smem, stream);
+        case 4: return launch_stream_v<FN, true, 4>(p, h, v, KP, smem, stream);
+    }
+    return launch_stream_v<FN, true, 8>(p, h, v, KP, smem, stream);
 }
 
 // ------------------------------------------------------------------------- //
@@ -2025,19 +2066,36 @@ __global__ __launch_bounds__(256, 3) void pair_mfma_kstream_kernel(StepArgs p, M
         }
 }
 
+// The instantiation of a k-streaming step (MfmaHints::stream == 2), pair_mfma_kstream_kernel<FN,VEC>, and its
+// workgroups -- four waves each, a slab per wave for splitk_reduce_kernel.  The one place that decides them, for the
+// launcher and for the name the executor reports (ctg_exec_step_kernel).
+struct KstreamVariant {
+    int fn;
+    bool vec;
+    int64_t blocks;   // (< 1: the scratch buffer holds no slab)
+};
+static KstreamVariant kstream_variant(const StepArgs& p, const MfmaHints& h, int64_t scratch_bytes) {
+    KstreamVariant v;
+    v.fn = h.bn / 16;
+    v.vec = h.vecA != 0;
+    const int64_t n_chunks = p.K / MFMA_BK;
+    v.blocks = 256 * 3;                             // resident: 3 blocks per CU
+    // at least 8 chunks per wave: every wave costs a slab in the final reduction
+    if (v.blocks * 32 > n_chunks) v.blocks = (n_chunks + 31) / 32;
+    const int64_t slab_bytes = 32 * 2 * 16 * v.fn * 4;
+    if (v.blocks * 4 * slab_bytes > scratch_bytes) v.blocks = scratch_bytes / slab_bytes / 4;
+    return v;
+}
+
 template <int FN>
 static hipError_t launch_kstream(const StepArgs& p, const MfmaHints& h, void* scratch,
                                  int64_t scratch_bytes, hipStream_t stream) {
     if (p.nz > 1)  // (per-wave partial tiles live in the one scratch buffer)
         return for_each_z(p, [&](const StepArgs& q) { return launch_kstream<FN>(q, h, scratch, scratch_bytes, stream); });
-    const int64_t n_chunks = p.K / MFMA_BK;
-    int64_t blocks = 256 * 3;                       // resident: 3 blocks per CU
-    // at least 8 chunks per wave: every wave costs a slab in the final reduction
-    if (blocks * 32 > n_chunks) blocks = (n_chunks + 31) / 32;
-    const int64_t slab_bytes = 32 * 2 * 16 * FN * 4;
-    if (blocks * 4 * slab_bytes > scratch_bytes) blocks = scratch_bytes / slab_bytes / 4;
+    const KstreamVariant v = kstream_variant(p, h, scratch_bytes);   // (v.fn == FN: launch_pair_mfma)
+    const int64_t blocks = v.blocks;
     if (blocks < 1) return hipErrorInvalidValue;
-    if (h.vecA)
+    if (v.vec)
         hipLaunchKernelGGL((pair_mfma_kstream_kernel<FN, true>), dim3((unsigned)blocks), dim3(256), 0, stream,
                            p, h, (float*)scratch);
     else
@@ -2127,8 +2185,16 @@ static hipError_t launch_skinny_t(const StepArgs& p, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// The instantiation of a skinny step (MfmaHints::stream == 3), pair_skinny_kernel<K,N>: for the launcher and for the
+// name the executor reports (ctg_exec_step_kernel).
+struct SkinnyVariant {
+    int k, n;
+};
+static SkinnyVariant skinny_variant(const StepArgs& p) { return SkinnyVariant{(int)p.K, (int)p.N}; }
+
 static hipError_t launch_skinny(const StepArgs& p, hipStream_t stream) {
-    switch ((int)p.K * 8 + (int)p.N) {
+    const SkinnyVariant v = skinny_variant(p);
+    switch (v.k * 8 + v.n) {
         case 2 * 8 + 1: return launch_skinny_t<2, 1>(p, stream);
         case 4 * 8 + 1: return launch_skinny_t<4, 1>(p, stream);
         case 8 * 8 + 1: return launch_skinny_t<8, 1>(p, stream);
@@ -2273,19 +2339,34 @@ static hipError_t launch_rowwise_t(const StepArgs& p, bool ts, dim3 grid, hipStr
     return hipGetLastError();
 }
 
+// The instantiation of a row-wise step (MfmaHints::stream == 4), pair_rowwise_kernel<NN,TS>: the one place that
+// decides it, for the launcher and for the name the executor reports (ctg_exec_step_kernel).
 // flags (MfmaHints::vecA of a row-wise step): bit 0 = the output columns are the
 // fastest-varying memory index of C
+struct RowwiseVariant {
+    int nn;    // accumulators per thread: N rounded up to 4, 8, 12, 16, 24 or 32
+    bool ts;   // the results of a block go through LDS
+};
+static RowwiseVariant rowwise_variant(const StepArgs& p, int flags) {
+    RowwiseVariant v;
+    v.nn = p.N <= 4 ? 4 : (p.N <= 8 ? 8 : (p.N <= 12 ? 12 : (p.N <= 16 ? 16 : (p.N <= 24 ? 24 : 32))));
+    v.ts = (flags & 1) && p.N >= 2;
+    return v;
+}
+
 static hipError_t launch_rowwise(const StepArgs& p, int flags, hipStream_t stream) {
     const int64_t blocks = (p.R + 255) / 256;
     if (blocks > 0x7fffffffll || p.nz > 65535 || !rowwise_ok(p)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks, (unsigned)p.nz, (unsigned)p.Bt);
-    const bool ts = (flags & 1) && p.N >= 2;
-    if (p.N <= 4) return launch_rowwise_t<4>(p, ts, grid, stream);
-    if (p.N <= 8) return launch_rowwise_t<8>(p, ts, grid, stream);
-    if (p.N <= 12) return launch_rowwise_t<12>(p, ts, grid, stream);
-    if (p.N <= 16) return launch_rowwise_t<16>(p, ts, grid, stream);
-    if (p.N <= 24) return launch_rowwise_t<24>(p, ts, grid, stream);
-    return launch_rowwise_t<32>(p, ts, grid, stream);
+    const RowwiseVariant v = rowwise_variant(p, flags);
+    switch (v.nn) {
+        case 4: return launch_rowwise_t<4>(p, v.ts, grid, stream);
+        case 8: return launch_rowwise_t<8>(p, v.ts, grid, stream);
+        case 12: return launch_rowwise_t<12>(p, v.ts, grid, stream);
+        case 16: return launch_rowwise_t<16>(p, v.ts, grid, stream);
+        case 24: return launch_rowwise_t<24>(p, v.ts, grid, stream);
+    }
+    return launch_rowwise_t<32>(p, v.ts, grid, stream);
 }
 
 template <typename Cfg>
@@ -2369,10 +2450,11 @@ hipError_t launch_pair_mfma(int dtype, const StepArgs& p, const MfmaHints& h, vo
         return hipErrorInvalidValue;
     }
     if (h.stream) {
+        const StreamVariant v = stream_variant(p, h);
         switch (h.bn) {
-            case 16: return launch_stream<1>(p, h, stream);
-            case 32: return launch_stream<2>(p, h, stream);
-            case 64: return launch_stream<4>(p, h, stream);
+            case 16: return launch_stream<1>(p, h, v, stream);
+            case 32: return launch_stream<2>(p, h, v, stream);
+            case 64: return launch_stream<4>(p, h, v, stream);
         }
         return hipErrorInvalidValue;
     }
@@ -2383,6 +2465,34 @@ hipError_t launch_pair_mfma(int dtype, const StepArgs& p, const MfmaHints& h, vo
         case 128: return launch_cfg<MfmaCfg<128, 128, 16, 2, 2>>(p, h, scratch, scratch_bytes, stream);
     }
     return hipErrorInvalidValue;
+}
+
+// The kernels launch_pair_mfma takes for a launch of this step with these hints, spelled with their template arguments;
+// a tiled step with k-splits and a k-streaming step name the pass that adds their slabs as well, and how many each
+// output has: " + splitk_reduce_kernel[S]".
+void pair_mfma_c64_name(const StepArgs& p, const MfmaHints& h, int64_t scratch_bytes, char* buf, size_t n) {
+    auto tf = [](bool b) { return b ? "true" : "false"; };
+    if (h.stream == 4) {
+        const RowwiseVariant v = rowwise_variant(p, h.vecA);
+        snprintf(buf, n, "pair_rowwise_kernel<%d,%s>", v.nn, tf(v.ts));
+    } else if (h.stream == 3) {
+        const SkinnyVariant v = skinny_variant(p);
+        snprintf(buf, n, "pair_skinny_kernel<%d,%d>", v.k, v.n);
+    } else if (h.stream == 2) {
+        const KstreamVariant v = kstream_variant(p, h, scratch_bytes);
+        snprintf(buf, n, "pair_mfma_kstream_kernel<%d,%s> + splitk_reduce_kernel[%lld]", v.fn, tf(v.vec),
+                 (long long)(v.blocks * 4));
+    } else if (h.stream) {
+        const StreamVariant v = stream_variant(p, h);
+        snprintf(buf, n, "pair_mfma_stream_kernel<%d,%s,%s,%s,%d>", v.fn, tf(v.vec), tf(v.add), tf(v.shortk), v.nv);
+    } else {
+        static const char* const kernels[] = {"pair_mfma_c64_kernel", "pair_mfma_fast_kernel", "pair_mfma_bf3_kernel",
+                                              "pair_mfma_h2_kernel"};
+        const TiledVariant v = tiled_variant(p, h, scratch_bytes);
+        const int len = snprintf(buf, n, "%s<128,%d,16>,%s", kernels[v.kernel], v.bn, tf(v.vec));
+        if (v.splits > 1 && len > 0 && (size_t)len < n)
+            snprintf(buf + len, n - (size_t)len, " + splitk_reduce_kernel[%lld]", (long long)v.splits);
+    }
 }
 
 }  // namespace ctg

@@ -2532,28 +2532,12 @@ int ctg_exec_step_kernel(ctg_exec* e, int64_t step, char* buf, int64_t buflen) {
     } else if (r[W_KERNEL] == KERNEL_MFMA && p->dtype != CTG_C64) {
         pair_mfma_real_name(p->dtype, e->args[step], e->hints[step].vecA, name, sizeof(name));
     } else if (r[W_KERNEL] == KERNEL_MFMA) {
-        const MfmaHints& h = e->hints[step];
-        if (h.stream == 4)
-            snprintf(name, sizeof(name), "pair_rowwise_kernel<%d>",
-                     r[W_N] <= 4 ? 4 : (r[W_N] <= 8 ? 8 : (r[W_N] <= 12 ? 12 : (r[W_N] <= 16 ? 16 : (r[W_N] <= 24 ? 24 : 32)))));
-        else if (h.stream == 3)
-            snprintf(name, sizeof(name), "pair_skinny_kernel<%d,%d>", (int)r[W_K], (int)r[W_N]);
-        else if (h.stream == 2)
-            snprintf(name, sizeof(name), "pair_mfma_kstream_kernel<%d,%s>", h.bn / 16, h.vecA ? "true" : "false");
-        else if (h.stream)
-            snprintf(name, sizeof(name), "pair_mfma_stream_kernel<%d,%s,%s,%s,%d>", h.bn / 16,
-                     (h.vecA && h.additive32) ? "true" : "false", h.additive32 ? "true" : "false",
-                     r[W_K] < MFMA_BK ? "true" : "false", r[W_K] <= 4 ? 2 : (r[W_K] <= 8 ? 4 : 8));
-        else if (h.bf3 && pair_bf16x3_on(e->args[step])) {
-            const bool h2 = pair_step_h2(e, tiled16_step(e, step) && h.splitk <= 1 && !e->grouped[step] &&
-                                               e->args[step].zqA <= 1 && e->args[step].zqB <= 1);
-            snprintf(name, sizeof(name), "%s<128,%d,16>,%s", h2 ? "pair_mfma_h2_kernel" : "pair_mfma_bf3_kernel", h.bn,
-                     h.vecA ? "true" : "false");
-        }
-        else
-            snprintf(name, sizeof(name), "%s<128,%d,16>,%s",
-                     h.fast ? "pair_mfma_fast_kernel" : "pair_mfma_c64_kernel", h.bn,
-                     h.vecA ? "true" : "false");
+        // (the instantiation, the k-splits and the pass that adds them: asked of the launcher's own rules, for the
+        // launch of one slice; the arithmetic of a long tiled step is decided here as launch_step decides it)
+        MfmaHints h = e->hints[step];
+        h.h2 = pair_step_h2(e, tiled16_step(e, step) && h.splitk <= 1 && !e->grouped[step] &&
+                                   e->args[step].zqA <= 1 && e->args[step].zqB <= 1) ? 1 : 0;
+        pair_mfma_c64_name(e->args[step], h, kScratchBytes, name, sizeof(name));
     } else {
         pair_valu_name(p->dtype, e->args[step], kScratchBytes, name, sizeof(name));
     }

@@ -284,6 +284,14 @@ int ctg_exec_profile_slice(ctg_exec* exec, int64_t slice_id, float* ms);
  * and complex128 spell out tile and gather width:
  *   "pair_mfma_c128_kernel<TM,TN>"                           e.g. <4,2>
  *   "pair_mfma_real_kernel<float|double,TM,TN,true|false>"   (last: 16-byte gathers)
+ * complex64 pair steps on the matrix-core route are one of
+ *   "pair_mfma_stream_kernel<FN,VEC,ADD,SHORTK,NV>"          e.g. <1,true,true,false,8>
+ *   "pair_rowwise_kernel<NN,TS>"                             e.g. <8,true>
+ *   "pair_skinny_kernel<K,N>"
+ *   "pair_mfma_kstream_kernel<FN,VEC> + splitk_reduce_kernel[S]"
+ *   "pair_mfma_{c64|fast|bf3|h2}_kernel<128,BN,16>,VEC"      tiled, one pass over k
+ *   "pair_mfma_{c64|fast|bf3}_kernel<128,BN,16>,VEC + splitk_reduce_kernel[S]"
+ * (S > 1 slabs of partial sums per output and the pass that adds them);
  * and the steps of every type that do not run on the matrix cores are
  *   "pair_valu_kernel"                                       a thread per output
  *   "pair_kred_kernel + pair_kred_finish_kernel<true|false>" lanes along a long k

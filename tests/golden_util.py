@@ -110,7 +110,8 @@ def stem_flags(name):
 
 def pair_flags(name):
     """What the executor says of a pair step in float32, float64 or complex128, or of a step of any type that does
-    not run on the matrix cores (include/ctg_hip.h: ctg_exec_step_kernel): ``kernel``, the name without template
+    not run on the matrix cores (include/ctg_hip.h: ctg_exec_step_kernel; complex64 on the matrix-core route:
+    pair_flags_c64): ``kernel``, the name without template
     arguments, and -- matrix-core kernels -- ``dtype`` ("float", "double" or "c128"), the MFMA tiles per wave
     ``tm``, ``tn`` and ``vec``, the 16-byte gathers (None in complex128); -- long contractions -- ``no``, the
     outputs a wave computes together (0: pair_kred_kernel, a wave per output), and ``finish_wave``, whether a
@@ -139,6 +140,40 @@ def pair_flags(name):
         out["finish_wave"] = w == "true"
     else:
         assert len(parts) == 1, name
+    return out
+
+
+C64_TILED = ("pair_mfma_c64_kernel", "pair_mfma_fast_kernel", "pair_mfma_bf3_kernel", "pair_mfma_h2_kernel")
+C64_KERNELS = C64_TILED + ("pair_mfma_stream_kernel", "pair_mfma_kstream_kernel", "pair_skinny_kernel", "pair_rowwise_kernel")
+
+
+def pair_flags_c64(name):
+    """What the executor says of a complex64 pair step on the matrix-core route (include/ctg_hip.h:
+    ctg_exec_step_kernel): ``kernel``, the name without template arguments; ``args``, its template arguments as a tuple
+    of ints and bools -- (FN, VEC, ADD, SHORTK, NV) streaming, (FN, VEC) k-streaming, (K, N) skinny, (NN, TS) row-wise,
+    (128, BN, 16) tiled --; ``vec``, the 16-byte gathers of a tiled kernel (written behind its tile, None elsewhere);
+    ``splits``, the slabs of partial sums that splitk_reduce_kernel adds per output (1: no such pass)."""
+    parts = [x.strip() for x in name.split(" + ")]
+    head = parts[0]
+    kernel = head.split("<")[0]
+    assert kernel in C64_KERNELS and "<" in head, name
+    inner, tail = head[head.index("<") + 1 : head.rindex(">")], head[head.rindex(">") + 1 :]
+    conv = {"true": True, "false": False}
+    args = tuple(conv[x.strip()] if x.strip() in conv else int(x) for x in inner.split(","))
+    out = {"kernel": kernel, "args": args, "vec": None, "splits": 1}
+    if kernel in C64_TILED:
+        assert tail in (",true", ",false") and len(args) == 3, name
+        out["vec"] = tail == ",true"
+    else:
+        assert tail == "", name
+        assert len(args) == (5 if kernel == "pair_mfma_stream_kernel" else 2), name
+    if len(parts) == 2:
+        assert kernel in C64_TILED[:3] + ("pair_mfma_kstream_kernel",), name
+        assert parts[1].startswith("splitk_reduce_kernel[") and parts[1].endswith("]"), name
+        out["splits"] = int(parts[1][len("splitk_reduce_kernel[") : -1])
+        assert out["splits"] > 1, name
+    else:
+        assert len(parts) == 1 and kernel != "pair_mfma_kstream_kernel", name
     return out
 
 

@@ -115,7 +115,7 @@ def split_contracted(case, fast):
     eq = case.eq.replace(k, k + "s" if fast else "s" + k)
     R, Bt, K, N = case.step
     new = Case(case.id + ("f" if fast else "s"), eq, dict(case.sizes, **{"s": p, k: ext // p}), (R, Bt, K // p, N),
-               tiles=[case.tiles[d] for d in DTYPES], seed=case.seed)
+               tiles=[case.tiles[d] for d in DTYPES] if case.tiles else None, seed=case.seed)
     new.split = k
     return new
 

@@ -1,7 +1,13 @@
 """Kernel-level GPU parity: single pairwise contractions with shuffled index
-layouts against numpy.einsum (complex128 accumulate), sized to hit every MFMA
-tile configuration, split-K, the k-reduction kernel, batch (hyper) indices,
-ragged tile edges and non-power-of-two extents."""
+layouts against numpy.einsum (complex128 accumulate) in all four types: tiled,
+streaming, k-streaming, row-wise and k-reduction steps, batch (hyper) indices,
+ragged tile edges and non-power-of-two extents.
+
+The numeric test asserts numbers, not kernels.  What each case runs in complex64 is
+pinned by test_pairwise_complex64_kernels below, so that a dispatcher rule that moves
+a case shows; every instantiation of the complex64 kernels, by name, is the business
+of tests/test_gpu_pair_variants_c64.py, the other three types' of
+tests/test_gpu_pair_variants.py."""
 import numpy as np
 import pytest
 
@@ -13,38 +19,38 @@ pytestmark = pytest.mark.gpu
 
 CASES = [
     # eq, sizes
-    ("abcd,cdef->abef", dict(a=16, b=32, c=8, d=4, e=8, f=8)),        # N=64 config
-    ("abcd,cdef->abef", dict(a=64, b=32, c=4, d=4, e=4, f=4)),        # N=16 config
-    ("abcd,cdef->feba", dict(a=64, b=32, c=4, d=4, e=8, f=4)),        # N=32, scattered output
-    ("dacb,fdce->abef", dict(a=16, b=32, c=8, d=4, e=8, f=8)),        # permuted operands
-    ("abk,kc->abc", dict(a=8, b=4, k=65536, c=32)),                   # split-K (32 x 65536 x 32)
-    ("ak,kb->ab", dict(a=2, k=1 << 18, b=2)),                         # k-reduction kernel
-    ("k,k->", dict(k=1 << 20)),                                       # dot product
-    ("xab,xbc->xac", dict(x=5, a=96, b=24, c=40)),                    # batch + ragged
-    ("axb,bxc->xca", dict(x=3, a=130, b=17, c=33)),                   # ragged everything
-    ("abc,cd->abd", dict(a=81, b=27, c=9, d=27)),                     # powers of three
-    ("ab,cd->abcd", dict(a=64, b=64, c=8, d=8)),                      # outer product
-    ("ab,ab->ab", dict(a=512, b=300)),                                # Hadamard
-    ("abc,bcd->ad", dict(a=4096, b=32, c=32, d=256)),                 # K=1024 GEMM
-    ("abcdefgh,hgfeij->abcdij", dict(a=8, b=8, c=8, d=8, e=2, f=2, g=2, h=2, i=4, j=4)),
-    # tall-skinny streaming kernel (R >= 8192, K <= 128, N <= 64)
-    ("abck,kn->abcn", dict(a=32, b=32, c=16, k=16, n=16)),            # 15: contiguous k
-    ("kabc,nk->cban", dict(a=32, b=32, c=16, k=32, n=32)),            # 16: k slowest, scattered out
-    ("akbc,kn->abcn", dict(a=64, b=16, c=16, k=128, n=64)),           # 17: K=128, N=64 (large LDS)
-    ("abkc,kn->abcn", dict(a=40, b=25, c=10, k=12, n=5)),             # 18: ragged R/K/N (general path)
-    ("abcdefghijklmnop,dhlp->abcefgijkmno", {ix: 2 for ix in "abcdefghijklmnop"}),  # 19: bit-permuted
-    ("abcdefghijklmnop,pdxhyl->xabcefygijkmno", {ix: 2 for ix in "abcdefghijklmnopxy"}),  # 20
-    # short contractions in the streaming kernel (only the real K columns are gathered)
-    ("abck,kn->abcn", dict(a=32, b=32, c=16, k=8, n=4)),              # 21: K=8
-    ("akbc,kn->abcn", dict(a=32, b=32, c=16, k=4, n=64)),             # 22: K=4, N=64
-    ("abcdefghijklmnop,dhpxy->abcefgijklmnoxy", {ix: 2 for ix in "abcdefghijklmnopxy"}),  # 23: K=8 bits
-    ("abkc,kn->abcn", dict(a=32, b=32, c=16, k=12, n=16)),            # 24: K=12
-    ("abck,kn->abcn", dict(a=32, b=32, c=16, k=2, n=8)),              # 25: K=2 streaming (pairs along k)
-    ("akbc,kn->abcn", dict(a=32, b=3, c=16, k=3, n=8)),               # 26: K=3 streaming, ragged rows
-    ("kabc,kn->abcn", dict(a=32, b=32, c=16, k=2, n=2)),              # 27: K=2, k slowest, N=2
-    ("ak,kb->ab", dict(a=20, k=1 << 17, b=9)),                        # 28: k-streaming, ragged R / N
-    ("ka,bk->ab", dict(a=32, k=1 << 16, b=16)),                       # 29: k-streaming, k slowest in A
-    ("aklm,mlkb->ba", dict(a=8, k=64, l=64, m=32, b=32)),             # 30: k-streaming, 3 contracted indices
+    ("abcd,cdef->abef", dict(a=16, b=32, c=8, d=4, e=8, f=8)),        # 0: N=64
+    ("abcd,cdef->abef", dict(a=64, b=32, c=4, d=4, e=4, f=4)),        # 1: N=16
+    ("abcd,cdef->feba", dict(a=64, b=32, c=4, d=4, e=8, f=4)),        # 2: N=32, scattered output
+    ("dacb,fdce->abef", dict(a=16, b=32, c=8, d=4, e=8, f=8)),        # 3: permuted operands
+    ("abk,kc->abc", dict(a=8, b=4, k=65536, c=32)),                   # 4: 32 x 65536 x 32
+    ("ak,kb->ab", dict(a=2, k=1 << 18, b=2)),                         # 5: k-reduction kernel
+    ("k,k->", dict(k=1 << 20)),                                       # 6: dot product
+    ("xab,xbc->xac", dict(x=5, a=96, b=24, c=40)),                    # 7: batch + ragged
+    ("axb,bxc->xca", dict(x=3, a=130, b=17, c=33)),                   # 8: ragged everything
+    ("abc,cd->abd", dict(a=81, b=27, c=9, d=27)),                     # 9: powers of three
+    ("ab,cd->abcd", dict(a=64, b=64, c=8, d=8)),                      # 10: outer product
+    ("ab,ab->ab", dict(a=512, b=300)),                                # 11: Hadamard
+    ("abc,bcd->ad", dict(a=4096, b=32, c=32, d=256)),                 # 12: K=1024 GEMM
+    ("abcdefgh,hgfeij->abcdij", dict(a=8, b=8, c=8, d=8, e=2, f=2, g=2, h=2, i=4, j=4)),   # 13
+    # tall-skinny steps (R >= 8192, K <= 128, N <= 64)
+    ("abck,kn->abcn", dict(a=32, b=32, c=16, k=16, n=16)),            # 14: contiguous k
+    ("kabc,nk->cban", dict(a=32, b=32, c=16, k=32, n=32)),            # 15: k slowest, scattered out
+    ("akbc,kn->abcn", dict(a=64, b=16, c=16, k=128, n=64)),           # 16: K=128, N=64
+    ("abkc,kn->abcn", dict(a=40, b=25, c=10, k=12, n=5)),             # 17: ragged R/K/N
+    ("abcdefghijklmnop,dhlp->abcefgijkmno", {ix: 2 for ix in "abcdefghijklmnop"}),  # 18: bit-permuted
+    ("abcdefghijklmnop,pdxhyl->xabcefygijkmno", {ix: 2 for ix in "abcdefghijklmnopxy"}),  # 19
+    # short contractions
+    ("abck,kn->abcn", dict(a=32, b=32, c=16, k=8, n=4)),              # 20: K=8, N=4
+    ("akbc,kn->abcn", dict(a=32, b=32, c=16, k=4, n=64)),             # 21: K=4, N=64
+    ("abcdefghijklmnop,dhpxy->abcefgijklmnoxy", {ix: 2 for ix in "abcdefghijklmnopxy"}),  # 22: K=8 bits, N=4
+    ("abkc,kn->abcn", dict(a=32, b=32, c=16, k=12, n=16)),            # 23: K=12
+    ("abck,kn->abcn", dict(a=32, b=32, c=16, k=2, n=8)),              # 24: K=2, N=8 (pairs along k)
+    ("akbc,kn->abcn", dict(a=32, b=3, c=16, k=3, n=8)),               # 25: K=3, ragged rows
+    ("kabc,kn->abcn", dict(a=32, b=32, c=16, k=2, n=2)),              # 26: K=2, k slowest, N=2
+    ("ak,kb->ab", dict(a=20, k=1 << 17, b=9)),                        # 27: ragged R / N under K = 2^17
+    ("ka,bk->ab", dict(a=32, k=1 << 16, b=16)),                       # 28: K = 2^16, k slowest in A
+    ("aklm,mlkb->ba", dict(a=8, k=64, l=64, m=32, b=32)),             # 29: K = 2^17 in 3 contracted indices
     # row-wise FMA kernel: tall steps, a handful of multiply-adds per row, odd extents / batch index
     ("abkc,kn->abcn", dict(a=27, b=32, c=27, k=4, n=4)),              # rows 3^6 * 2^5, 4 columns
     ("akbc,knm->abcnm", dict(a=16, b=8, c=81, k=6, n=3, m=3)),         # K = 6, N = 9 (12-column variant)
@@ -94,6 +100,73 @@ def test_pairwise(case, dtype):
     assert np.abs(np.asarray(got) - ref).max() <= tol * scale, (np.abs(np.asarray(got) - ref).max() / scale, tol)
 
 
+# The kernels case 0, 1, ... runs in complex64, as the executor names them (without the count of slabs).  When a
+# dispatcher rule moves a case, this list says so; the variant it left is still run by
+# tests/test_gpu_pair_variants_c64.py.
+PAIRWISE_C64 = [
+    "pair_mfma_fast_kernel<128,16,16>,true",
+    "pair_mfma_fast_kernel<128,16,16>,true",
+    "pair_mfma_fast_kernel<128,16,16>,true",
+    "pair_mfma_fast_kernel<128,16,16>,true",
+    "pair_mfma_kstream_kernel<2,true> + splitk_reduce_kernel",
+    "pair_kred_multi_kernel<4> + pair_kred_finish_kernel<true>",
+    "pair_kred_kernel + pair_kred_finish_kernel<true>",
+    "pair_mfma_c64_kernel<128,16,16>,false",
+    "pair_mfma_c64_kernel<128,16,16>,false",
+    "pair_mfma_c64_kernel<128,16,16>,false",
+    "pair_valu_kernel",
+    "pair_valu_kernel",
+    "pair_mfma_fast_kernel<128,128,16>,true + splitk_reduce_kernel",
+    "pair_mfma_fast_kernel<128,16,16>,true",
+    "pair_mfma_stream_kernel<1,true,true,false,8>",
+    "pair_mfma_stream_kernel<2,true,true,false,8>",
+    "pair_mfma_fast_kernel<128,16,16>,true",
+    "pair_rowwise_kernel<8,true>",
+    "pair_valu_kernel",
+    "pair_valu_kernel",
+    "pair_rowwise_kernel<4,true>",
+    "pair_mfma_stream_kernel<4,true,true,true,2>",
+    "pair_rowwise_kernel<4,true>",
+    "pair_mfma_stream_kernel<1,true,true,true,8>",
+    "pair_rowwise_kernel<8,true>",
+    "pair_valu_kernel",
+    "pair_rowwise_kernel<4,true>",
+    "pair_kred_kernel + pair_kred_finish_kernel<true>",
+    "pair_mfma_kstream_kernel<1,true> + splitk_reduce_kernel",
+    "pair_mfma_kstream_kernel<1,true> + splitk_reduce_kernel",
+    "pair_rowwise_kernel<4,true>",
+    "pair_rowwise_kernel<12,true>",
+    "pair_rowwise_kernel<24,true>",
+    "pair_rowwise_kernel<4,true>",
+    "pair_rowwise_kernel<8,true>",
+    "pair_rowwise_kernel<4,false>",
+    "pair_rowwise_kernel<32,true>",
+    "pair_rowwise_kernel<32,true>",
+    "pair_rowwise_kernel<32,true>",
+    "pair_kred_multi_kernel<3> + pair_kred_finish_kernel<true>",
+    "pair_kred_multi_kernel<3> + pair_kred_finish_kernel<true>",
+    "pair_kred_multi_kernel<4> + pair_kred_finish_kernel<true>",
+    "pair_kred_multi_kernel<2> + pair_kred_finish_kernel<true>",
+]
+
+
+@pytest.mark.parametrize("case", range(len(CASES)))
+def test_pairwise_complex64_kernels(case):
+    import re
+
+    from cotengra_amd.contractor import HipContractor
+
+    eq, sizes = CASES[case]
+    (ta, tb), out = ca.eq_to_inputs_output(eq)
+    fn = HipContractor(ca.ContractionTree.from_path([ta, tb], out, sizes, path=[(0, 1)]))
+    try:
+        st = fn.setup(*[np.zeros([sizes[i] for i in t], dtype="complex64") for t in (ta, tb)])
+        names = [n for n in st["exec"].step_kernels() if n.startswith("pair_")]
+    finally:
+        fn.close()
+    assert [re.sub(r"\[\d+\]$", "", n) for n in names] == [PAIRWISE_C64[case]], names
+
+
 SKINNY = [
     # rows paired along the fastest index of A and C, K a power of two, N in {1, 2, 4}
     ("kabc,kn->abcn", dict(a=64, b=64, c=32, k=8, n=2)),
@@ -102,6 +175,11 @@ SKINNY = [
     ("kabc,kn->abcn", dict(a=128, b=64, c=32, k=2, n=1)),
     ("ajbklc,ljkn->abcn", dict(a=32, b=64, c=64, j=2, k=2, l=2, n=2)),   # three contracted bits
 ]
+
+
+# the instantiation each of them takes (the other five of the nine: tests/pair_variant_cases_c64.py)
+SKINNY_KERNELS = ["pair_skinny_kernel<8,2>", "pair_skinny_kernel<4,4>", "pair_skinny_kernel<16,1>", "pair_skinny_kernel<2,1>",
+                  "pair_skinny_kernel<8,2>"]
 
 
 @pytest.mark.parametrize("case", range(len(SKINNY)))
@@ -121,7 +199,7 @@ def test_skinny_kernel(case):
     fn = HipContractor(tree)
     st = fn.setup(*arrays)
     names = [n for n in st["exec"].step_kernels() if n.startswith("pair_")]
-    assert names and all(n.startswith("pair_skinny_kernel") for n in names), names
+    assert names == [SKINNY_KERNELS[case]], names
     got = np.asarray(fn(*arrays))
     ref = np.einsum(eq, *[x.astype("complex128") for x in arrays], optimize=True)
     assert got.shape == ref.shape

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """HBM traffic of the MFMA pair kernels from two rocprofv3 PMC passes.
 
-  python tools/pmc_traffic.py <fetch.db> <write.db> <slices_in_run> <out.json> [<tree file name>]
+  python tools/pmc_traffic.py <fetch.db> <write.db> <slices_in_run> <out.json> [<tree file name> [<steps.json>]]
 
 FETCH_SIZE / WRITE_SIZE are in KiB.  Per MI355X_MICROARCH.md (HBM section) on
 gfx950 FETCH_SIZE reports exactly half of the bytes of a wide coalesced
@@ -9,9 +9,16 @@ streaming read (64 B tallied per 128 B request), so reads are doubled;
 WRITE_SIZE is used as is (it reproduces the algorithmic write bytes of the
 plan to 4 digits, see the JSON).  The two counters need separate passes
 (TCC slots).
+
+The executor names a tiled step with k-splits and a k-streaming step with both of its launches,
+"<kernel> + splitk_reduce_kernel[S]"; rocprof sees two kernels and no S.  Given <steps.json> (bench.py
+--dump-steps of the same tree) the summary also lists the first launch's counters under every such step
+name, which is what a join on step names (bench.py: pmc_traffic_for) looks up; without it such steps
+find no entry.  tools/final_measure.sh and tools/pmc_only.sh pass it.
 """
 import collections
 import json
+import os
 import re
 import sqlite3
 import sys
@@ -29,9 +36,9 @@ def step_kernel_name(rocprof_name):
     m = re.match(r"pair_mfma_kstream_kernel<(\d+), (true|false)>", rocprof_name)
     if m:
         return f"pair_mfma_kstream_kernel<{m.group(1)},{m.group(2)}>"
-    m = re.match(r"pair_rowwise_kernel<(\d+), (?:true|false)>", rocprof_name)
+    m = re.match(r"pair_rowwise_kernel<(\d+), (true|false)>", rocprof_name)
     if m:
-        return f"pair_rowwise_kernel<{m.group(1)}>"
+        return f"pair_rowwise_kernel<{m.group(1)},{m.group(2)}>"
     m = re.match(r"(stem2h?_kernel)<([^>]*)>", rocprof_name)
     if m:   # (template arguments spelled as csrc/ctg_stem.hip: stem2_kernel_name spells them; stem2h: fp16 x 2)
         return "%s<%s>" % (m.group(1), m.group(2).replace(" ", ""))
@@ -39,6 +46,19 @@ def step_kernel_name(rocprof_name):
     if m:
         return f"pair_skinny_kernel<{m.group(1)},{m.group(2)}>"
     return rocprof_name.split("<")[0]
+
+
+def reduced_step_names(steps_json):
+    """Step names that carry a second launch (" + splitk_reduce_kernel[S]": a tiled step with k-splits, a k-streaming
+    step), by the name of their first one -- rocprof knows the two launches apart, a step's name holds both."""
+    heads = collections.defaultdict(set)
+    if not os.path.exists(steps_json):
+        return heads
+    for r in json.load(open(steps_json)):
+        name = r.get("kernel_name") or ""
+        if " + splitk_reduce_kernel[" in name:
+            heads[name.split(" + ")[0]].add(name)
+    return heads
 
 
 def per_kernel(path, cname):
@@ -70,9 +90,23 @@ def main():
             tot_f += fb
             tot_w += wb
             launches += f[k][0]
+    # (optional sixth argument: bench.py --dump-steps of the same tree -- the counters of a kernel also under the
+    # names of the steps that run it with a reduction pass behind it, so that a join on step names finds them)
+    if len(sys.argv) > 6:
+        for head, full in reduced_step_names(sys.argv[6]).items():
+            for name in full:
+                if head in kernels:
+                    # (the kernel's counters over ALL steps that run it, per launch -- and, where rocprof saw it,
+                    # the reduction pass's bytes per launch next to them)
+                    red = kernels.get("splitk_reduce_kernel")
+                    kernels.setdefault(name, dict(kernels[head], first_launch_only=True,
+                                                  reduce_hbm_bytes_per_launch=red["hbm_bytes_per_launch"] if red else None))
     res = {
         "tree": tree,
-        "counters": "FETCH_SIZE (x2 gfx950 correction), WRITE_SIZE; separate rocprofv3 --pmc passes",
+        "counters": "FETCH_SIZE (x2 gfx950 correction), WRITE_SIZE; separate rocprofv3 --pmc passes.  An entry named "
+                    "'<kernel> + splitk_reduce_kernel[S]' (first_launch_only) repeats the counters of <kernel> -- all of "
+                    "its launches, with k-splits or without -- and leaves the reduction pass out of hbm_bytes_per_launch: "
+                    "that pass's bytes per launch, over all steps, are reduce_hbm_bytes_per_launch",
         "slices_in_run": nsl,
         "mfma_launches": launches,
         "mfma_fetch_bytes_per_slice": tot_f / nsl,
