@@ -181,3 +181,103 @@ def absorb_low_rank(tensors, keep=()):
             alive.discard(t)
             changed = True
     return [tensors[t] for t in sorted(alive)]
+
+
+# ---------------------------------------------------------------------------------------------------- #
+# sampling: fix most qubits at random, leave a few open, draw from the conditional distribution
+# ---------------------------------------------------------------------------------------------------- #
+#
+# What quimb offers as ``Circuit.sample_chaotic`` on top of the reference: for a chaotic circuit the
+# marginal of a random assignment of the fixed qubits is as good as a draw from it, so a bunch of
+# samples costs ONE contraction with the ``marginal_qubits`` open -- a batch of 2^k amplitudes that
+# stays on the device, where ``HipContractor.sample`` draws from it.
+
+
+def _check_marginal(n, marginal_qubits):
+    qs = sorted(int(q) for q in marginal_qubits)
+    if not qs:
+        raise ValueError("marginal_qubits is empty: leave at least one qubit open.")
+    if len(set(qs)) != len(qs):
+        raise ValueError(f"marginal_qubits {list(marginal_qubits)} repeats a qubit.")
+    if qs[0] < 0 or qs[-1] >= n:
+        raise ValueError(f"marginal_qubits {list(marginal_qubits)} outside the {n} qubits.")
+    return qs
+
+
+def chaotic_prefixes(n, marginal_qubits, bunches=1, seed=None):
+    """The bitstring templates of ``sample_chaotic``'s bunches (``'?'`` at the marginal qubits, a random bit
+    at every other one) and the generator that drew them, which goes on to draw the uniforms -- a pure
+    function of ``seed``."""
+    qs = set(_check_marginal(n, marginal_qubits))
+    bunches = int(bunches)
+    if bunches < 1:
+        raise ValueError(f"bunches = {bunches}: need at least one.")
+    rng = np.random.default_rng(seed)
+    templates = []
+    for _ in range(bunches):
+        bits = rng.integers(0, 2, size=n)
+        templates.append("".join("?" if q in qs else str(int(bits[q])) for q in range(n)))
+    return templates, rng
+
+
+def sample_chaotic(n, gates, n_samples, marginal_qubits, bunches=1, seed=None, optimize="greedy",
+                   dtype="complex64", target_size=None):
+    """Bitstrings of the ``n``-qubit circuit ``gates`` by the fix-and-marginalise scheme: ``bunches`` times,
+    fix every qubit outside ``marginal_qubits`` to a random bit, contract the batch of ``2^k`` amplitudes of
+    the open ones on the device and draw ``n_samples // bunches`` of its members from ``|amplitude|^2``
+    there (``HipContractor.sample``) -- only indices, the drawn amplitudes and the norm come back.
+
+    The network is built and its tree found once (``optimize``: as for ``array_contract_tree``, e.g. a
+    ``ContractionTree`` over the network of any template; ``target_size`` slices the tree found); a bunch
+    only rebuilds and uploads the arrays, the structure of the network not depending on the bit values.
+
+    Returns a dict: ``bitstrings`` (one ``'0'/'1'`` string of ``n`` characters per draw, bunch after
+    bunch), ``amplitudes`` (of those bitstrings), ``p`` (their ``|amplitude|^2``), ``bunch`` (which bunch
+    each draw belongs to), and per bunch ``prefixes`` (its template, ``'?'`` at the marginal qubits),
+    ``norms`` (``sum |amplitude|^2`` of its batch: the marginal probability of its fixed bits) and
+    ``sum_p2``."""
+    from .interface import array_contract_tree
+
+    n_samples = int(n_samples)
+    if n_samples < 0:
+        raise ValueError(f"n_samples = {n_samples} is negative.")
+    qs = _check_marginal(n, marginal_qubits)
+    templates, rng = chaotic_prefixes(n, qs, bunches, seed)
+    per = n_samples // len(templates)
+    inputs, output, size_dict, arrays = circuit_to_network(n, gates, templates[0], simplify=True, dtype=dtype)
+    tree = array_contract_tree(inputs, output, size_dict, optimize=optimize)
+    if [tuple(t) for t in tree.inputs] != [tuple(t) for t in inputs] or tuple(tree.output) != tuple(output):
+        raise ValueError("optimize: the tree is not over this circuit's network.")
+    if target_size is not None:
+        tree = tree.slice(target_size=target_size)
+    out = {"bitstrings": [], "amplitudes": [], "p": [], "bunch": [], "prefixes": templates, "norms": [], "sum_p2": []}
+    for b, template in enumerate(templates):
+        if b:
+            inputs_b, output_b, _, arrays = circuit_to_network(n, gates, template, simplify=True, dtype=dtype)
+            assert inputs_b == inputs and output_b == output, "the network's structure depends on the bit values"
+        res = tree.contract_sample(arrays, per, uniforms=rng.random(per))
+        for coords in res.coords:
+            bits = list(template)
+            for q, c in zip(qs, coords):
+                bits[q] = str(int(c))
+            out["bitstrings"].append("".join(bits))
+        out["amplitudes"].append(res.amplitudes)
+        out["p"].append(res.p)
+        out["bunch"].append(np.full(per, b, dtype=np.int64))
+        out["norms"].append(res.norm)
+        out["sum_p2"].append(res.sum_p2)
+    for key in ("amplitudes", "p", "bunch"):
+        out[key] = np.concatenate(out[key])
+    out["norms"] = np.asarray(out["norms"])
+    out["sum_p2"] = np.asarray(out["sum_p2"])
+    return out
+
+
+def linear_xeb(n_qubits, probabilities):
+    """Linear cross-entropy benchmark fidelity of sampled bitstrings with ideal probabilities
+    ``probabilities``: ``2^n mean(p) - 1`` (1 for draws from a Porter-Thomas distribution, 0 for uniform
+    ones)."""
+    p = np.asarray(probabilities, dtype=np.float64)
+    if p.size == 0:
+        raise ValueError("linear_xeb of no samples.")
+    return float(2.0 ** int(n_qubits) * p.mean() - 1.0)

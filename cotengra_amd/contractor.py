@@ -15,6 +15,7 @@ input space, result returned as a torch tensor on the same device).
 
 from __future__ import annotations
 
+import collections
 import time
 
 import threading
@@ -210,6 +211,17 @@ def _autograd_function():
 
     _ContractFunction = ContractFunction
     return ContractFunction
+
+
+class SampleResult(collections.namedtuple(
+        "SampleResult", "indices coords amplitudes p norm sum_p2 max_p argmax exponent")):
+    """What ``HipContractor.sample`` returns: ``indices`` ``(n,)`` int64 flat row-major positions in the result
+    (``tree.gathered_shape()``), ``coords`` ``(n, len(output))`` the same as one value per output index,
+    ``amplitudes`` / ``p`` the elements drawn and their ``|x|^2`` (float64); and of the whole result ``norm`` =
+    ``sum |x|^2``, ``sum_p2`` = ``sum |x|^4``, ``max_p`` with its lowest flat index ``argmax``, and the
+    base-10 ``exponent`` taken out under ``strip_exponent`` (0.0 otherwise)."""
+
+    __slots__ = ()
 
 
 class HipContractor:
@@ -610,6 +622,44 @@ class HipContractor:
             ex.run_slices(int(i), 1, 1)
             index = _chunk_index(self.tree, self.tree.slice_key(int(i)))
             return self._finish(st, strip_exponent, check_zero, index=index)
+
+    def sample(self, *arrays, n_samples, seed=None, uniforms=None, strip_exponent=False, check_zero=False):
+        """Contract (all slices, as a call does) and draw ``n_samples`` members of the result from
+        ``p = |x|^2 / sum |x|^2`` on the device -- the result tensor is never copied to the host
+        (``ctg_exec_sample_result``).  The draws are the inverse CDF at ``uniforms``
+        (values in ``[0, 1)``; default ``np.random.default_rng(seed).random(n_samples)``): the same inputs and
+        uniforms give the same draws.  Returns a :class:`SampleResult`.  With ``strip_exponent`` the amplitudes,
+        ``p``, ``norm``, ``sum_p2`` and ``max_p`` are the mantissa's (true values: ``x 10^exponent``,
+        ``10^(2 exponent)``, ``10^(2 exponent)``, ``10^(4 exponent)``, ``10^(2 exponent)``).  ``ValueError``
+        when the result is all zero or not finite.  Not differentiable."""
+        n_samples = int(n_samples)
+        if n_samples < 0:
+            raise ValueError(f"n_samples = {n_samples} is negative.")
+        if uniforms is None:
+            u = np.random.default_rng(seed).random(n_samples)
+        else:
+            u = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(-1)
+            if u.size != n_samples:
+                raise ValueError(f"{u.size} uniforms for n_samples = {n_samples}.")
+        if not np.all((u >= 0.0) & (u < 1.0)):   # (also refuses NaN; the library checks again)
+            raise ValueError("uniforms must lie in [0, 1).")
+        with self._lock:
+            st = self.setup(*arrays)
+            ex = st["exec"]
+            ex.set_strip_exponent(strip_exponent, check_zero)
+            ex.zero_result()
+            self.run_share(ex, 0, 1, False)
+            if n_samples:
+                idx, amps, p = ex.sample_result(u)
+                norm, sum_p2, max_p, argmax = ex.sample_info()[:4]   # (of the passes the draws just ran)
+            else:
+                idx, amps, p = ex.sample_result(u)
+                norm, sum_p2, max_p, argmax = ex.result_stats()
+            exponent = ex.get_exponent()[0] if strip_exponent else 0.0
+        shape = tuple(self.tree.gathered_shape())
+        coords = np.stack(np.unravel_index(idx, shape), axis=1).astype(np.int64) if shape else np.zeros((idx.size, 0), np.int64)
+        return SampleResult(indices=idx, coords=coords, amplitudes=amps, p=p, norm=norm, sum_p2=sum_p2, max_p=max_p,
+                            argmax=argmax, exponent=exponent)
 
     def profile(self, arrays, slice_id=0):
         """Per-step milliseconds for one slice (see ``Plan.describe_steps``)."""

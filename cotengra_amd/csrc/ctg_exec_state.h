@@ -144,6 +144,17 @@ struct ctg_exec {
     int64_t group_key = -1;
     ctg::StripState* d_strip = nullptr;
     int64_t root_step = -1;
+    // (ABI 9) statistics of / draws from the result tensor (ctg_sample.hip): the per-block sums and their prefix
+    // sums, the uniforms and outputs of one chunk of draws -- allocated by the first call, grown on demand
+    void* d_sample_blocks = nullptr;
+    void* d_sample_io = nullptr;
+    int64_t sample_blocks_bytes = 0, sample_io_bytes = 0;
+    // what the last statistics / sample call found ({sum p, sum p^2, max p, bits of argmax}) and the device time of its
+    // passes 1 and 2 (events on the executor's stream): ctg_exec_sample_info
+    double sample_last[4] = {0, 0, 0, 0};
+    float sample_pass_ms[2] = {0, 0};
+    bool sample_last_valid = false;
+    hipEvent_t sample_ev[3] = {nullptr, nullptr, nullptr};
 };
 
 

@@ -1809,6 +1809,10 @@ int ctg_exec_destroy(ctg_exec* e) {
     if (e->d_counted) (void)hipFree(e->d_counted);
     if (e->d_fac_zero) (void)hipFree(e->d_fac_zero);
     if (e->d_strip) (void)hipFree(e->d_strip);
+    if (e->d_sample_blocks) (void)hipFree(e->d_sample_blocks);
+    if (e->d_sample_io) (void)hipFree(e->d_sample_io);
+    for (hipEvent_t ev : e->sample_ev)
+        if (ev) (void)hipEventDestroy(ev);
     delete e;
     return CTG_OK;
 }
@@ -2421,6 +2425,7 @@ int ctg_exec_device_bytes(ctg_exec* e, int64_t* bytes) {
     if (e->owns_result) n += p->result_elems * isz;
     if (e->d_wide) n += p->result_elems * 2 * isz;
     if (e->d_scratch) n += e->scratch_total;
+    n += e->sample_blocks_bytes + e->sample_io_bytes;   // (ctg_sample.hip: allocated by the first statistics / draw)
     *bytes = n;
     return CTG_OK;
 }

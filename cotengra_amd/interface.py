@@ -189,6 +189,19 @@ class ContractExpression:
             _close_all(victims)                 # outside the cache lock, see _trim_expression_cache
         return out
 
+    def sample(self, *arrays, n_samples, **kwargs):
+        """``expr(*arrays)`` followed by ``n_samples`` draws from ``|result|^2`` on the device
+        (``HipContractor.sample``); the expression's own ``strip_exponent`` / ``check_zero`` unless given."""
+        kwargs.setdefault("strip_exponent", self.fn.strip_exponent)
+        kwargs.setdefault("check_zero", self.fn.check_zero)
+        out = self.fn.sample(*arrays, n_samples=n_samples, **kwargs)
+        if self._cached:
+            self._bytes = self.device_bytes()
+            with _EXPR_LOCK:
+                victims = _trim_expression_cache(keep=self)
+            _close_all(victims)
+        return out
+
     def device_bytes(self):
         """Device memory this expression's executors hold right now (``ctg_exec_device_bytes``:
         arena x slice batch, inputs, tables, result, scratch), read under the contractor's lock

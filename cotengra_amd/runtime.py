@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 _LIB_PATH = os.environ.get("CTG_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libctg_hip.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 # every symbol include/ctg_hip.h declares
 SYMBOLS = (
@@ -44,6 +44,9 @@ SYMBOLS = (
     "ctg_exec_step_kernel",
     "ctg_exec_sync",
     "ctg_exec_result_ptr",
+    "ctg_exec_result_stats",
+    "ctg_exec_sample_result",
+    "ctg_exec_sample_info",
     "ctg_exec_download_result",
     "ctg_exec_download_arena",
     "ctg_exec_get_state",
@@ -152,6 +155,10 @@ def load():
         "ctg_exec_step_kernel": [vp, C.c_int64, C.c_char_p, C.c_int64],
         "ctg_exec_sync": [vp],
         "ctg_exec_result_ptr": [vp, C.POINTER(vp)],
+        "ctg_exec_result_stats": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), i64p],
+        "ctg_exec_sample_result": [vp, C.POINTER(C.c_double), C.c_int64, i64p, vp, C.POINTER(C.c_double)],
+        "ctg_exec_sample_info": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), i64p,
+                                 C.POINTER(C.c_float)],
         "ctg_exec_download_result": [vp, vp],
         "ctg_exec_download_arena": [vp, C.c_int64, C.c_int64, vp],
         "ctg_exec_get_state": [vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_int)],
@@ -189,7 +196,7 @@ def load():
 def _check(rc):
     if rc != 0:
         msg = load().ctg_last_error().decode("utf-8", "replace")
-        if rc == -1:
+        if rc in (-1, -6):   # (CTG_E_INVALID; CTG_E_NORM: nothing to draw from)
             raise ValueError(msg)
         if rc == -3:
             raise MemoryError(msg)
@@ -408,6 +415,38 @@ class Executor:
         out = np.empty(self.plan.result_shape, dtype=np.dtype(self.plan.dtype))
         _check(load().ctg_exec_download_result(self.handle, C.c_void_p(out.ctypes.data)))
         return out
+
+    # -- statistics of / draws from the result tensor (csrc/ctg_sample.hip) -- #
+
+    def result_stats(self):
+        """``(sum p, sum p^2, max p, argmax)`` of ``p = |x|^2`` over the result tensor, summed in double on the
+        device (``ctg_exec_result_stats``); the mantissa's values under ``strip_exponent``."""
+        s, q, m, i = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
+        _check(load().ctg_exec_result_stats(self.handle, C.byref(s), C.byref(q), C.byref(m), C.byref(i)))
+        return s.value, q.value, m.value, i.value
+
+    def sample_result(self, uniforms):
+        """One draw from ``p / sum p`` per uniform in ``[0, 1)`` by inverse CDF on the device
+        (``ctg_exec_sample_result``): ``(flat indices, the elements there, their p)``.  ``ValueError`` for a
+        uniform outside ``[0, 1)`` (nothing is launched) and for a result whose ``sum p`` is zero or not finite."""
+        u = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(-1)
+        n = u.size
+        idx = np.empty(n, dtype=np.int64)
+        elems = np.empty(n, dtype=np.dtype(self.plan.dtype))
+        p = np.empty(n, dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        _check(load().ctg_exec_sample_result(self.handle, u.ctypes.data_as(dp), n, _i64p(idx),
+                                             C.c_void_p(elems.ctypes.data), p.ctypes.data_as(dp)))
+        return idx, elems, p
+
+    def sample_info(self):
+        """``(sum p, sum p^2, max p, argmax, (pass 1 ms, pass 2 ms))`` of the last ``result_stats`` /
+        ``sample_result`` call -- the tensor as it was then -- without touching the device
+        (``ctg_exec_sample_info``)."""
+        s, q, m, i = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
+        ms = (C.c_float * 2)()
+        _check(load().ctg_exec_sample_info(self.handle, C.byref(s), C.byref(q), C.byref(m), C.byref(i), ms))
+        return s.value, q.value, m.value, i.value, (ms[0], ms[1])
 
     # -- checkpoint state (include/ctg_hip.h: ctg_exec_get_state / set_state) -- #
 

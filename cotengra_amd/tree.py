@@ -1052,6 +1052,14 @@ class ContractionTree:
 
         return _tree_contractor(self, order).vjp(*arrays, cotangent=cotangent, wrt=wrt)
 
+    def contract_sample(self, arrays, n_samples, order=None, **kwargs):
+        """:meth:`contract` followed by ``n_samples`` draws from ``|result|^2`` on the device, the result
+        tensor staying there: indices, coordinates, amplitudes and the batch's norm
+        (``HipContractor.sample``; ``kwargs``: ``seed``, ``uniforms``, ``strip_exponent``, ``check_zero``)."""
+        from .contractor import _tree_contractor
+
+        return _tree_contractor(self, order).sample(*arrays, n_samples=n_samples, **kwargs)
+
     def contract_resumable(self, arrays, checkpoint, **kwargs):
         """:meth:`contract` with a checkpoint file: the partial sum over slices
         is saved every ``every`` slices and an interrupted run continues from

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CTG_ABI_VERSION 8
+#define CTG_ABI_VERSION 9
 
 /* element types of the tensors (reference tests cover all four:
  * tests/test_compute.py:102-115) */
@@ -41,7 +41,8 @@ enum {
     CTG_E_HIP = -2,     /* a HIP runtime call failed */
     CTG_E_NOMEM = -3,   /* device allocation failed */
     CTG_E_BOUNDS = -4,  /* plan addresses outside a declared buffer */
-    CTG_E_COMM = -5     /* RCCL missing, or a collective call failed */
+    CTG_E_COMM = -5,    /* RCCL missing, or a collective call failed */
+    CTG_E_NORM = -6     /* (ABI 9) nothing to draw from: the result tensor's sum of |x|^2 is zero or not finite */
 };
 
 #define CTG_STEP_WORDS 48
@@ -248,7 +249,8 @@ int ctg_plan_share_slice_ids(const ctg_plan* plan, int64_t rank, int64_t world, 
 int ctg_exec_run_share(ctg_exec* exec, int64_t rank, int64_t world, int64_t unit_first, int64_t unit_count);
 /* ABI 4.  Device memory this executor holds right now: inputs space, arena x slice batch,
  * tables, the result if it owns it, the scratch buffer if the plan has a step that needs one
- * (allocated by ctg_exec_create).  What a cache of contractors -- the reference keeps them
+ * (allocated by ctg_exec_create), the scratch of ctg_exec_result_stats / ctg_exec_sample_result once they
+ * have run (ABI 9).  What a cache of contractors -- the reference keeps them
  * on the tree, core.py:3708-3722 -- has to count against its budget. */
 int ctg_exec_device_bytes(ctg_exec* exec, int64_t* bytes);
 /* ABI 5.  Is there a kernel instantiation for a three-step tile of this shape (stem steps fused
@@ -306,6 +308,35 @@ int ctg_exec_sync(ctg_exec* exec);
 int ctg_exec_result_ptr(ctg_exec* exec, void** dev_ptr);
 /* synchronous copy of the result to host memory */
 int ctg_exec_download_result(ctg_exec* exec, void* host_out);
+/* ABI 9.  What a caller wants from an amplitude batch (a tree with open output qubits; quimb's
+ * `Circuit.sample_chaotic` on top of the reference) without moving the batch to the host: statistics of, and draws
+ * from, p_i = |x_i|^2 over the result tensor -- result_elems elements, row-major in the tree's output order, whoever
+ * owns the memory -- as it stands after the work already enqueued on the executor's stream.  p is formed and summed
+ * in double for every element type (re*re + im*im; an fp32 square of a deep circuit's amplitude is zero), by three
+ * kernels of fixed summation order (csrc/ctg_sample.hip): the same tensor and the same
+ * uniforms give the same bits on every run and every executor.  Both calls synchronise the stream.  For a
+ * single-precision sliced tree they read the result tensor (the double-precision sum of the slices rounded once),
+ * not the wide sum.  There is no multi-rank entry: after ctg_exec_reduce the root's (every rank's, for an
+ * all-reduce) result tensor holds the total and the same calls work there.  Not differentiable.
+ * The scratch (40 bytes per 4096 elements, 40 per draw of a chunk of at most 2^18) is allocated by the first call,
+ * grown on demand, counted by ctg_exec_device_bytes and freed by ctg_exec_destroy. */
+/* sum|x|^2, sum|x|^4, max|x|^2 and its (lowest) flat index over the result tensor, in double (each may be NULL).
+ * Under strip_exponent the values are the mantissa's; the true ones are x 10^(2E), 10^(4E), 10^(2E). */
+int ctg_exec_result_stats(ctg_exec* exec, double* sum_p, double* sum_p2, double* max_p, int64_t* argmax);
+/* n draws from p_i / sum p by inverse CDF: u[s] in [0,1) (host) -> idx[s] (host, flat row-major index): the
+ * element at which the running sum of p first exceeds u[s] * sum p, up to the rounding of two summation orders
+ * (|error| <= 2 * result_elems * 2^-53 * sum p on that target); never an element with p = 0.  Where non-NULL,
+ * elems[s] (plan dtype) and p[s] (double) receive the element at idx[s] and its p.  CTG_E_INVALID for a null
+ * exec / u / idx, n < 0, a uniform outside [0,1) or NaN -- checked on the host before anything is launched;
+ * CTG_E_NORM when sum p is zero or not finite.  n = 0 succeeds and does nothing.  The uniforms are the caller's:
+ * the call is a pure function of (result tensor, u), the generator is the host's choice. */
+int ctg_exec_sample_result(ctg_exec* exec, const double* u, int64_t n, int64_t* idx, void* elems, double* p);
+/* What the last ctg_exec_result_stats / ctg_exec_sample_result call on this executor found -- the four statistics
+ * of the tensor AS IT WAS THEN (a caller that has just drawn needs no second pass over the tensor for its norm) --
+ * and, where pass_ms is non-NULL, pass_ms[0..1]: the device time in milliseconds of that call's pass 1
+ * (prob_block_kernel) and pass 2 (prob_scan_kernel), from events on the executor's stream.  Any pointer may be NULL.
+ * CTG_E_INVALID when no such call has completed.  Host only: launches and copies nothing. */
+int ctg_exec_sample_info(ctg_exec* exec, double* sum_p, double* sum_p2, double* max_p, int64_t* argmax, float* pass_ms);
 /* debugging aid: copy `n` elements of the arena starting at element `offset`
  * to the host (synchronous) */
 int ctg_exec_download_arena(ctg_exec* exec, int64_t offset, int64_t n, void* host_out);
