@@ -16,6 +16,7 @@ input space, result returned as a torch tensor on the same device).
 from __future__ import annotations
 
 import collections
+import os
 import time
 
 import threading
@@ -257,6 +258,7 @@ class HipContractor:
         fuse=None,
         fuse_min_elems=None,
         stem_bf16x3=None,
+        crest_limit=None,
     ):
         self._origin = tree  # whose ``contraction_cores`` hold this contractor's siblings
         if handle_slicing or not tree.sliced_inds:
@@ -278,6 +280,19 @@ class HipContractor:
         # (round 6) a string names the arithmetic outright: "fp32", "bf16x3" (three exact limbs, six products) or
         # "fp16x2" (two limbs, three products: what an executor takes when nothing is said); True / False as
         # before: bf16 x 3 / fp32
+        # "auto" (with crest_limit=L, required -- no threshold has been measured, so there is no default): every call
+        # audits slice 0 in bf16 x 3 and takes fp16 x 2 only if every tensor it would scale per tensor has
+        # crest_up <= L and no inf / NaN (rangeaudit.auto_choice); CTG_STEM_ARITH in the environment wins
+        self.auto_arith = stem_bf16x3 == "auto"
+        if self.auto_arith:
+            if crest_limit is None:
+                raise ValueError('stem_bf16x3="auto" needs crest_limit (there is no default: no threshold has been measured).')
+            stem_bf16x3 = "bf16x3"
+        elif crest_limit is not None:
+            raise ValueError('crest_limit is the threshold of stem_bf16x3="auto" only.')
+        self.crest_limit = None if crest_limit is None else float(crest_limit)
+        self.last_audit = None
+        self.arithmetic_chosen = None
         self.stem_arith = stem_bf16x3 if isinstance(stem_bf16x3, str) else None
         if isinstance(stem_bf16x3, str):
             stem_bf16x3 = stem_bf16x3 != "fp32"
@@ -390,7 +405,11 @@ class HipContractor:
             )
         else:
             st["exec"] = runtime.Executor(dplan, device=device)
-        if self.stem_arith is not None:
+        if self.auto_arith and (vjp or os.environ.get("CTG_STEM_ARITH")):
+            # (the environment's arithmetic, which the executor took when it was created; a VJP executor: below)
+            if vjp:
+                st["exec"].set_stem_arithmetic("bf16x3")
+        elif self.stem_arith is not None:
             st["exec"].set_stem_arithmetic(self.stem_arith)
         elif self.stem_bf16x3 is not None:
             st["exec"].set_stem_arithmetic(self.stem_bf16x3)
@@ -603,10 +622,59 @@ class HipContractor:
             return _autograd_function().apply(self, progbar, check_zero, *arrays)
         return self._contract(arrays, progbar, check_zero, strip_exponent)
 
+    # ---- range audit (csrc/ctg_range.hip, cotengra_amd/rangeaudit.py) ----------------------- #
+
+    def _audit_resident(self, ex, slices):
+        """Audit ``slices`` of the inputs resident in ``ex`` in its current arithmetic; the result is left zeroed."""
+        from . import rangeaudit
+
+        ex.set_strip_exponent(False, False)
+        names = ex.step_kernels()
+        audits = []
+        try:
+            for s in slices:
+                ex.zero_result()
+                audits.append(ex.range_audit(int(s)))
+        finally:
+            ex.zero_result()
+        return rangeaudit.step_records(ex.plan, names, audits)
+
+    def audit(self, *arrays, slices=(0,)):
+        """Upload ``arrays``, run the slices ``slices`` step by step in the executor's current arithmetic and read
+        every tensor on the way (``ctg_exec_range_audit``): one record per plan step -- the kernel name, a
+        ``rangeaudit.RangeSummary`` of operands ``a``, ``b`` (``b2`` of a fused pair) and of the result ``c``
+        (``None``: not materialised, e.g. a member of an LDS-resident subtree), ``scaled``: the operands that
+        run under a per-tensor scale, and ``kappa = |A| |B| (|B2|) / |C|``.  Several slices: the worst value per
+        field.  float32 / complex64 only.  The result tensor is left zeroed."""
+        with self._lock:
+            st = self.setup(*arrays)
+            return self._audit_resident(st["exec"], tuple(slices))
+
+    def _choose_arithmetic(self, ex):
+        """``stem_bf16x3="auto"``: set the arithmetic of ``ex`` for the inputs resident in it."""
+        if not self.auto_arith:
+            return
+        from . import rangeaudit
+
+        if os.environ.get("CTG_STEM_ARITH"):
+            self.arithmetic_chosen = "environment"
+            return
+        if ex.plan.dtype not in ("float32", "complex64"):
+            # (double precision has no reduced arithmetic: nothing to choose)
+            self.arithmetic_chosen = "bf16x3"
+            return
+        ex.set_stem_arithmetic("fp16x2")
+        h2_names = ex.step_kernels()
+        ex.set_stem_arithmetic("bf16x3")
+        self.last_audit = self._audit_resident(ex, (0,))
+        self.arithmetic_chosen = rangeaudit.auto_choice(h2_names, self.last_audit, self.crest_limit)
+        ex.set_stem_arithmetic(self.arithmetic_chosen)
+
     def _contract(self, arrays, progbar, check_zero, strip_exponent):
         with self._lock:
             st = self.setup(*arrays)
             ex = st["exec"]
+            self._choose_arithmetic(ex)
             ex.set_strip_exponent(strip_exponent, check_zero)
             ex.zero_result()
             self.run_share(ex, 0, 1, progbar)
@@ -617,6 +685,7 @@ class HipContractor:
         with self._lock:
             st = self.setup(*arrays)
             ex = st["exec"]
+            self._choose_arithmetic(ex)
             ex.set_strip_exponent(strip_exponent, check_zero)
             ex.zero_result()
             ex.run_slices(int(i), 1, 1)
@@ -646,6 +715,7 @@ class HipContractor:
         with self._lock:
             st = self.setup(*arrays)
             ex = st["exec"]
+            self._choose_arithmetic(ex)
             ex.set_strip_exponent(strip_exponent, check_zero)
             ex.zero_result()
             self.run_share(ex, 0, 1, False)

@@ -155,6 +155,10 @@ struct ctg_exec {
     float sample_pass_ms[2] = {0, 0};
     bool sample_last_valid = false;
     hipEvent_t sample_ev[3] = {nullptr, nullptr, nullptr};
+    // (ABI 10) the range audit (ctg_range.hip, ctg_exec_range_audit): [rows (n_inputs + n_steps) x CTG_RANGE_WORDS |
+    // sums of squares | the pass's per-workgroup rows] -- allocated by the first call, grown on demand
+    void* d_range = nullptr;
+    int64_t range_bytes = 0;
 };
 
 
@@ -172,6 +176,18 @@ namespace ctg {
 // (nz slices from z on: the record (kMaxSub floats, zeroed by the caller) at out + i * out_zs for slice z + i)
 hipError_t launch_maxabs_f32(const void* base, const int64_t* soff, int64_t z, int64_t zs, int64_t zstride, int64_t n,
                              float* out, hipStream_t stream, int nz = 1, int out_zs = 0);
+}
+
+namespace ctg {
+// (ctg_range.hip) exponent histogram, zero count and sum of squares of n contiguous fp32 components at x:
+// row <- {1, n, zeros, 0, hist[256]} and *sumsq (device memory), through `partials` (range_partial_bytes(blocks)
+// bytes of device memory, blocks >= range_blocks(n)).  Reads [x, x + n) only; the caller checks that range.
+constexpr int64_t kRangeMaxBlocks = 2048;              // workgroups of the pass (a workgroup takes several chunks)
+constexpr int64_t kRangeMaxComponents = 1ll << 40;     // (a workgroup's 32-bit counts hold its share)
+int64_t range_blocks(int64_t n);
+int64_t range_partial_bytes(int64_t blocks);
+hipError_t launch_range_hist(const void* x, int64_t n, void* partials, int64_t blocks, int64_t* row, double* sumsq,
+                             hipStream_t stream);
 }
 
 // LDS-resident subtrees (ctg_lds_host.hip): descriptor validation (host only) and per-executor packing

@@ -1811,6 +1811,7 @@ int ctg_exec_destroy(ctg_exec* e) {
     if (e->d_strip) (void)hipFree(e->d_strip);
     if (e->d_sample_blocks) (void)hipFree(e->d_sample_blocks);
     if (e->d_sample_io) (void)hipFree(e->d_sample_io);
+    if (e->d_range) (void)hipFree(e->d_range);
     for (hipEvent_t ev : e->sample_ev)
         if (ev) (void)hipEventDestroy(ev);
     delete e;
@@ -2426,6 +2427,7 @@ int ctg_exec_device_bytes(ctg_exec* e, int64_t* bytes) {
     if (e->d_wide) n += p->result_elems * 2 * isz;
     if (e->d_scratch) n += e->scratch_total;
     n += e->sample_blocks_bytes + e->sample_io_bytes;   // (ctg_sample.hip: allocated by the first statistics / draw)
+    n += e->range_bytes;                                // (ctg_range.hip: allocated by the first range audit)
     *bytes = n;
     return CTG_OK;
 }
@@ -2505,6 +2507,120 @@ int ctg_exec_profile_slice(ctg_exec* e, int64_t slice_id, float* ms) {
     HIP_TRY(hipStreamSynchronize(e->stream));
     for (int64_t s = 0; s < p->n_steps; ++s)
         HIP_TRY(hipEventElapsedTime(&ms[s], e->events[s], e->events[s + 1]));
+    return CTG_OK;
+}
+
+// (ABI 10) One slice as ctg_exec_profile_slice launches it, the range pass (ctg_range.hip) behind every step whose
+// result lies in the arena, and once over every input tensor.
+int ctg_exec_range_audit(ctg_exec* e, int64_t slice_id, int64_t* rows, double* sumsq) {
+    if (!e || !rows || !sumsq) return fail(CTG_E_INVALID, "null argument");
+    const ctg_plan* p = e->plan;
+    if (p->dtype != CTG_F32 && p->dtype != CTG_C64)
+        return fail(CTG_E_INVALID, "range audit: float32 and complex64 plans only (double precision has no reduced arithmetic)");
+    if (e->strip) return fail(CTG_E_INVALID, "range audit: not under strip_exponent (the stored values are not the logical ones)");
+    if (slice_id < 0 || slice_id >= p->nslices) return fail(CTG_E_INVALID, "slice id out of range");
+    const int64_t T = p->n_inputs + p->n_steps;
+    const int64_t isz = kItemSize[p->dtype], comps = isz / 4;
+    // a step's result is materialised where the audit can read it: in the arena, not an accumulate step, not a
+    // member of an LDS-resident subtree (slice-invariant steps always launch on their own: run_invariants)
+    auto audited = [&](int64_t s) {
+        const int64_t* r = &p->steps[s * STEP_WORDS];
+        if (r[W_KIND] == KIND_ACCUM || r[W_C_SPACE] != SPACE_ARENA) return false;
+        return e->invariant[s] || e->lds_comp_of.empty() || e->lds_comp_of[s] < 0;
+    };
+    // every range the pass is going to read, checked against its space before anything is launched (and again in
+    // front of each launch, below): ctg_plan_create does not hold the size words against the space
+    auto in_space = [&](int64_t off, int64_t size, int64_t space) {
+        return off >= 0 && size >= 0 && size <= space && off <= space - size && size <= kRangeMaxComponents / comps;
+    };
+    int64_t blocks = 1;
+    for (int64_t i = 0; i < p->n_inputs; ++i) {
+        if (!in_space(p->input_offsets[i], p->input_sizes[i], p->inputs_elems))
+            return fail(CTG_E_BOUNDS, "range audit: input %lld (offset %lld, size %lld) outside the inputs space (%lld)", (long long)i,
+                        (long long)p->input_offsets[i], (long long)p->input_sizes[i], (long long)p->inputs_elems);
+        blocks = std::max(blocks, range_blocks(p->input_sizes[i] * comps));
+    }
+    for (int64_t s = 0; s < p->n_steps; ++s) {
+        if (!audited(s)) continue;
+        const int64_t* r = &p->steps[s * STEP_WORDS];
+        if (!in_space(r[W_C_OFF], r[W_C_SIZE], p->arena_elems))
+            return fail(CTG_E_BOUNDS, "range audit: result of step %lld (offset %lld, size %lld) outside the arena (%lld)", (long long)s,
+                        (long long)r[W_C_OFF], (long long)r[W_C_SIZE], (long long)p->arena_elems);
+        blocks = std::max(blocks, range_blocks(r[W_C_SIZE] * comps));
+    }
+    e->group_key = -1;   // (every step of this slice is launched: whatever a group shared before is overwritten)
+    HIP_TRY(hipSetDevice(e->device));
+    const int64_t rows_bytes = T * CTG_RANGE_WORDS * 8, head = rows_bytes + T * 8;
+    const int64_t want = head + range_partial_bytes(blocks);
+    if (e->range_bytes < want) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        if (e->d_range) {
+            HIP_TRY(hipFree(e->d_range));
+            e->d_range = nullptr;
+            e->range_bytes = 0;
+        }
+        HIP_TRY(hipMalloc(&e->d_range, (size_t)want));
+        e->range_bytes = want;
+    }
+    int64_t* d_rows = (int64_t*)e->d_range;
+    double* d_sumsq = (double*)((char*)e->d_range + rows_bytes);
+    void* d_part = (char*)e->d_range + head;
+    const int64_t part_blocks = (e->range_bytes - head) / range_partial_bytes(1);
+    HIP_TRY(hipMemsetAsync(e->d_range, 0, (size_t)head, e->stream));
+    // the pass over `size` elements at element `off` of a space of `space` elements starting at `base` -> row t
+    auto pass = [&](const char* base, int64_t off, int64_t size, int64_t space, int64_t t) -> int {
+        if (!in_space(off, size, space)) return fail(CTG_E_BOUNDS, "range audit: tensor %lld outside its space", (long long)t);
+        const hipError_t err = launch_range_hist(base + off * isz, size * comps, d_part, part_blocks,
+                                                 d_rows + t * CTG_RANGE_WORDS, d_sumsq + t, e->stream);
+        if (err != hipSuccess) return fail(CTG_E_HIP, "range pass launch failed: %s", hipGetErrorString(err));
+        return CTG_OK;
+    };
+    for (int64_t i = 0; i < p->n_inputs; ++i) {
+        const int rc = pass(e->d_inputs, p->input_offsets[i], p->input_sizes[i], p->inputs_elems, i);
+        if (rc != CTG_OK) return rc;
+    }
+    {
+        const int rc = run_invariants(e);
+        if (rc != CTG_OK) return rc;
+    }
+    // (slice-invariant results persist at their arena range, which no later step recycles: read there, whether this
+    // call or an earlier one computed them)
+    for (int64_t s = 0; s < p->n_steps; ++s) {
+        if (!e->invariant[s] || !audited(s)) continue;
+        const int64_t* r = &p->steps[s * STEP_WORDS];
+        const int rc = pass(e->d_arena, r[W_C_OFF], r[W_C_SIZE], p->arena_elems, p->n_inputs + s);
+        if (rc != CTG_OK) return rc;
+    }
+    hipError_t err = launch_prologue(e->meta, e->d_state, e->d_soff, slice_id, e->stream, 1, 1);
+    if (err != hipSuccess) return fail(CTG_E_HIP, "prologue launch failed: %s", hipGetErrorString(err));
+    bool lds_done[2] = {false, false};
+    for (int64_t s = 0; s < p->n_steps; ++s) {
+        if (e->invariant[s]) continue;
+        if (!e->lds_comp_of.empty() && e->lds_comp_of[s] >= 0) {
+            // a member of an LDS-resident subtree: all subtrees of its class are ONE launch (ctg_exec_profile_slice)
+            const int cls = e->grouped[s] ? 0 : 1;
+            if (!lds_done[cls] && p->steps[s * STEP_WORDS + W_KIND] == KIND_PAIR) {
+                lds_done[cls] = true;
+                const ctg_exec::Issue q{s, -2, e->lds_first[cls], e->lds_count[cls], (uint32_t)e->lds_count[cls], cls == 0};
+                const int rc = launch_issue(e, q, 1, e->stream);
+                if (rc != CTG_OK) return rc;
+            }
+            continue;
+        }
+        {
+            const int rc = launch_step(e, s, e->stream);
+            if (rc != CTG_OK) return rc;
+        }
+        if (!audited(s)) continue;
+        // replica 0 of the arena: the launch carries one slice (the range launch_step's own max-abs pass reads
+        // under strip_exponent)
+        const int64_t* r = &p->steps[s * STEP_WORDS];
+        const int rc = pass(e->d_arena, r[W_C_OFF], r[W_C_SIZE], p->arena_elems, p->n_inputs + s);
+        if (rc != CTG_OK) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(rows, d_rows, (size_t)rows_bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(sumsq, d_sumsq, (size_t)(T * 8), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return CTG_OK;
 }
 

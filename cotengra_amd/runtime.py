@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 _LIB_PATH = os.environ.get("CTG_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libctg_hip.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # every symbol include/ctg_hip.h declares
 SYMBOLS = (
@@ -47,6 +47,7 @@ SYMBOLS = (
     "ctg_exec_result_stats",
     "ctg_exec_sample_result",
     "ctg_exec_sample_info",
+    "ctg_exec_range_audit",
     "ctg_exec_download_result",
     "ctg_exec_download_arena",
     "ctg_exec_get_state",
@@ -159,6 +160,7 @@ def load():
         "ctg_exec_sample_result": [vp, C.POINTER(C.c_double), C.c_int64, i64p, vp, C.POINTER(C.c_double)],
         "ctg_exec_sample_info": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), i64p,
                                  C.POINTER(C.c_float)],
+        "ctg_exec_range_audit": [vp, C.c_int64, i64p, C.POINTER(C.c_double)],
         "ctg_exec_download_result": [vp, vp],
         "ctg_exec_download_arena": [vp, C.c_int64, C.c_int64, vp],
         "ctg_exec_get_state": [vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_int)],
@@ -447,6 +449,23 @@ class Executor:
         ms = (C.c_float * 2)()
         _check(load().ctg_exec_sample_info(self.handle, C.byref(s), C.byref(q), C.byref(m), C.byref(i), ms))
         return s.value, q.value, m.value, i.value, (ms[0], ms[1])
+
+    # -- range audit (csrc/ctg_range.hip, cotengra_amd/rangeaudit.py) -- #
+
+    RANGE_WORDS = 260
+
+    def range_audit(self, slice_id=0):
+        """Run slice ``slice_id`` step by step in the executor's current arithmetic, adding it to the result as
+        ``run_slices(slice_id, 1, 1)`` would, and read every tensor on the way (``ctg_exec_range_audit``):
+        ``(rows, sumsq)`` with ``rows[(n_inputs + n_steps), 260]`` int64 -- status, component count, zeros, 0 and
+        the 256 counts by biased fp32 exponent -- and ``sumsq[n_inputs + n_steps]`` float64; rows of the input
+        tensors first, then one per plan step.  ``rangeaudit.summarise`` reads a row.  ``ValueError`` for a
+        double-precision plan, under ``strip_exponent`` and for a slice outside the tree."""
+        t = len(self.plan.input_sizes) + len(self.plan.steps)
+        rows = np.zeros((t, self.RANGE_WORDS), dtype=np.int64)
+        sumsq = np.zeros(t, dtype=np.float64)
+        _check(load().ctg_exec_range_audit(self.handle, int(slice_id), _i64p(rows), sumsq.ctypes.data_as(C.POINTER(C.c_double))))
+        return rows, sumsq
 
     # -- checkpoint state (include/ctg_hip.h: ctg_exec_get_state / set_state) -- #
 

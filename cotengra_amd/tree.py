@@ -1060,6 +1060,14 @@ class ContractionTree:
 
         return _tree_contractor(self, order).sample(*arrays, n_samples=n_samples, **kwargs)
 
+    def contract_audit(self, arrays, slices=(0,), order=None):
+        """Range audit of the contraction on ``arrays`` (``HipContractor.audit``): the
+        slices ``slices`` run step by step, one record per plan step with the exponent statistics of its
+        operands and result, which of them run under a per-tensor scale, and how far the step cancels."""
+        from .contractor import _tree_contractor
+
+        return _tree_contractor(self, order).audit(*arrays, slices=slices)
+
     def contract_resumable(self, arrays, checkpoint, **kwargs):
         """:meth:`contract` with a checkpoint file: the partial sum over slices
         is saved every ``every`` slices and an interrupted run continues from

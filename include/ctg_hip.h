@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CTG_ABI_VERSION 9
+#define CTG_ABI_VERSION 10
 
 /* element types of the tensors (reference tests cover all four:
  * tests/test_compute.py:102-115) */
@@ -337,6 +337,35 @@ int ctg_exec_sample_result(ctg_exec* exec, const double* u, int64_t n, int64_t* 
  * (prob_block_kernel) and pass 2 (prob_scan_kernel), from events on the executor's stream.  Any pointer may be NULL.
  * CTG_E_INVALID when no such call has completed.  Host only: launches and copies nothing. */
 int ctg_exec_sample_info(ctg_exec* exec, double* sum_p, double* sum_p2, double* max_p, int64_t* argmax, float* pass_ms);
+/* ABI 10.  Range audit (csrc/ctg_range.hip): where the components of every tensor of one slice
+ * lie below the tensor's largest one.  The fp16 x 2 arithmetic keeps one power of two per operand tensor, so its
+ * error is a fraction of the tensor's LARGEST element; this call measures what that means for the data at hand.
+ * float32 and complex64 plans only (CTG_E_INVALID otherwise: double-precision trees have no reduced arithmetic), not
+ * under strip_exponent (CTG_E_INVALID: the stored values are not the logical ones there, and fp16 x 2 is off).
+ *
+ * The call runs slice `slice_id` as ctg_exec_profile_slice does -- every step launched on its own, LDS-resident
+ * subtrees as their one launch, slice-invariant steps once per upload, the executor's current arithmetic -- and adds
+ * the slice into the result tensor, as run_slices(slice_id, 1, 1) would.  After every step whose result lies in the
+ * arena it reads that result (its W_C_SIZE contiguous elements, as n fp32 components: 2 per complex64 element).
+ * rows[(n_inputs + n_steps) * CTG_RANGE_WORDS] and sumsq[n_inputs + n_steps] (host) receive, for the input tensors
+ * (rows 0 .. n_inputs - 1: the whole leaf as stored in the inputs space, after the upload's power-of-two scaling,
+ * which moves all bins of a tensor together) and the result of step s (row n_inputs + s):
+ *   word 0        1: audited; 0: not materialised (a member of an LDS-resident subtree, an accumulate step, a
+ *                 result outside the arena) -- the other words are 0 then
+ *   word 1        number of components
+ *   word 2        components equal to +-0
+ *   word 3        reserved (0)
+ *   word 4 + b    components whose biased exponent field (bits >> 23) & 0xff is b: b = 0 zeros and subnormals,
+ *                 b = 255 inf and NaN
+ *   sumsq         sum of x^2 over the finite components, each square formed in double, summed in a fixed order
+ * The same bytes give the same numbers on every run and on every executor (integer counts; no float atomics).
+ * Before every pass the host checks offset + size of the tensor against its space: CTG_E_BOUNDS, nothing is read.
+ * CTG_E_INVALID for null pointers and a slice id outside [0, nslices).  Synchronous.  The pass only reads; a later
+ * call returns what it would return on an executor that had run the slice with run_slices.  The scratch (a few MiB
+ * at most) is allocated by the first call, grown on demand, counted by ctg_exec_device_bytes and freed by
+ * ctg_exec_destroy. */
+#define CTG_RANGE_WORDS 260
+int ctg_exec_range_audit(ctg_exec* exec, int64_t slice_id, int64_t* rows, double* sumsq);
 /* debugging aid: copy `n` elements of the arena starting at element `offset`
  * to the host (synchronous) */
 int ctg_exec_download_arena(ctg_exec* exec, int64_t offset, int64_t n, void* host_out);
