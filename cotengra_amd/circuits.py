@@ -273,6 +273,52 @@ def sample_chaotic(n, gates, n_samples, marginal_qubits, bunches=1, seed=None, o
     return out
 
 
+def top_chaotic(n, gates, marginal_qubits, bunches=1, top=1, seed=None, optimize="greedy", dtype="complex64",
+                target_size=None):
+    """The post-selection companion of :func:`sample_chaotic`: the same bunches (``chaotic_prefixes``: every qubit
+    outside ``marginal_qubits`` fixed to a random bit), the same single tree and executor, but of every bunch's
+    batch of ``2^k`` amplitudes the ``top`` heaviest members, selected on the device (``HipContractor.topk``) --
+    ``|amplitude|^2`` descending, the lower bitstring first among equals.
+
+    Returns a dict: ``bitstrings`` (``top`` per bunch, bunch after bunch, heaviest first), ``amplitudes``, ``p``
+    (their ``|amplitude|^2``), ``bunch``, and per bunch ``prefixes``, ``norms`` (``sum |amplitude|^2`` of its
+    batch) and ``sum_p2``."""
+    from .interface import array_contract_tree
+
+    top = int(top)
+    qs = _check_marginal(n, marginal_qubits)
+    if top < 1 or top > 2 ** len(qs):
+        raise ValueError(f"top = {top}: a bunch has {2 ** len(qs)} members.")
+    templates, _ = chaotic_prefixes(n, qs, bunches, seed)
+    inputs, output, size_dict, arrays = circuit_to_network(n, gates, templates[0], simplify=True, dtype=dtype)
+    tree = array_contract_tree(inputs, output, size_dict, optimize=optimize)
+    if [tuple(t) for t in tree.inputs] != [tuple(t) for t in inputs] or tuple(tree.output) != tuple(output):
+        raise ValueError("optimize: the tree is not over this circuit's network.")
+    if target_size is not None:
+        tree = tree.slice(target_size=target_size)
+    out = {"bitstrings": [], "amplitudes": [], "p": [], "bunch": [], "prefixes": templates, "norms": [], "sum_p2": []}
+    for b, template in enumerate(templates):
+        if b:
+            inputs_b, output_b, _, arrays = circuit_to_network(n, gates, template, simplify=True, dtype=dtype)
+            assert inputs_b == inputs and output_b == output, "the network's structure depends on the bit values"
+        res = tree.contract_topk(arrays, top)
+        for coords in res.coords:
+            bits = list(template)
+            for q, c in zip(qs, coords):
+                bits[q] = str(int(c))
+            out["bitstrings"].append("".join(bits))
+        out["amplitudes"].append(res.amplitudes)
+        out["p"].append(res.p)
+        out["bunch"].append(np.full(top, b, dtype=np.int64))
+        out["norms"].append(res.norm)
+        out["sum_p2"].append(res.sum_p2)
+    for key in ("amplitudes", "p", "bunch"):
+        out[key] = np.concatenate(out[key])
+    out["norms"] = np.asarray(out["norms"])
+    out["sum_p2"] = np.asarray(out["sum_p2"])
+    return out
+
+
 def linear_xeb(n_qubits, probabilities):
     """Linear cross-entropy benchmark fidelity of sampled bitstrings with ideal probabilities
     ``probabilities``: ``2^n mean(p) - 1`` (1 for draws from a Porter-Thomas distribution, 0 for uniform

@@ -225,6 +225,51 @@ class SampleResult(collections.namedtuple(
     __slots__ = ()
 
 
+class TopKResult(collections.namedtuple("TopKResult", "indices coords amplitudes p norm sum_p2 exponent")):
+    """What ``HipContractor.topk`` returns: the ``k`` most probable members of the result, ``p`` descending and the
+    lower flat index first among equal ``p`` -- ``indices`` ``(k,)`` int64 flat row-major positions in the result
+    (``tree.gathered_shape()``), ``coords`` ``(k, len(output))``, ``amplitudes`` and their ``p = |x|^2`` (float64);
+    and of the whole result ``norm`` = ``sum |x|^2``, ``sum_p2`` = ``sum |x|^4`` and the base-10 ``exponent`` taken
+    out under ``strip_exponent`` (0.0 otherwise)."""
+
+    __slots__ = ()
+
+
+class MarginalResult(collections.namedtuple("MarginalResult", "p norm exponent")):
+    """What ``HipContractor.marginal`` returns: ``p`` the array of ``sum |x|^2`` over the output indices not kept,
+    its axes in the order the caller named the labels (a list of such arrays for a list of requests); ``norm`` =
+    ``sum |x|^2`` of the whole result; the base-10 ``exponent`` taken out under ``strip_exponent`` (0.0 otherwise:
+    true values are ``p 10^(2 exponent)``)."""
+
+    __slots__ = ()
+
+
+def _marginal_requests(tree, keep):
+    """``keep`` of ``HipContractor.marginal`` as ``(several?, [(labels, keep flags per output axis, shape in the
+    tensor's order, permutation to the caller's order), ...])`` -- host only; ``ValueError`` for a label that is
+    not an output index of ``tree`` or that is named twice."""
+    output = list(tree.output)
+    shape = tuple(tree.gathered_shape())
+    if isinstance(keep, (str, bytes)) or not hasattr(keep, "__iter__"):
+        raise ValueError(f"keep = {keep!r}: give a sequence of output index labels, or a list of such sequences.")
+    keep = list(keep)
+    several = bool(keep) and all(isinstance(q, (list, tuple, set, frozenset)) for q in keep)
+    reqs = []
+    for labels in (keep if several else [keep]):
+        labels = list(labels)
+        for ix in labels:
+            if ix not in output:
+                raise ValueError(f"keep: {ix!r} is not an output index of the tree (output: {output}).")
+        if len(set(labels)) != len(labels):
+            raise ValueError(f"keep: {labels} repeats a label.")
+        flags = [1 if ix in labels else 0 for ix in output]
+        kept = [ix for ix in output if ix in labels]                 # (the tensor's own order)
+        kshape = tuple(d for d, f in zip(shape, flags) if f)
+        perm = tuple(kept.index(ix) for ix in labels)
+        reqs.append((labels, flags, kshape, perm))
+    return several, reqs
+
+
 class HipContractor:
     """Callable performing the contraction of ``tree`` on an MI355X.
 
@@ -303,6 +348,9 @@ class HipContractor:
         # are cached on the tree and in the expression cache, and the reference's callers may
         # be multi-threaded (presets.py:77-88): upload -> run -> fetch is one critical section.
         self._lock = threading.RLock()
+        # (executor state, strip_exponent) of the call made last if it left the whole contraction in the result
+        # tensor (__call__, sample, topk, marginal), None after anything else: what reuse=True reads (under _lock)
+        self._reusable = None
 
     # ------------------------------------------------------------------ #
 
@@ -422,6 +470,7 @@ class HipContractor:
     def setup(self, *arrays):
         """Make ``arrays`` resident and return the executor state (the
         analogue of ``CuQuantumContractor.setup``, contract.py:883-899)."""
+        self._reusable = None
         if len(arrays) != self.tree.N:
             raise ValueError(
                 f"Expected {self.tree.N} arrays, got {len(arrays)}."
@@ -463,6 +512,7 @@ class HipContractor:
         """Upload ``arrays`` and ``cotangent`` to the VJP executor of ``wrt`` (cached in ``_execs`` with
         the mask in the key, so that the out-of-memory eviction covers it) and return its state."""
         tree = self.tree
+        self._reusable = None
         if len(arrays) != tree.N:
             raise ValueError(f"Expected {tree.N} arrays, got {len(arrays)}.")
         for i, (x, s) in enumerate(zip(arrays, tree.get_shapes())):
@@ -678,6 +728,7 @@ class HipContractor:
             ex.set_strip_exponent(strip_exponent, check_zero)
             ex.zero_result()
             self.run_share(ex, 0, 1, progbar)
+            self._reusable = (st, bool(strip_exponent))
             return self._finish(st, strip_exponent, check_zero)
 
     def contract_slice(self, arrays, i, strip_exponent=False, check_zero=False):
@@ -726,10 +777,85 @@ class HipContractor:
                 idx, amps, p = ex.sample_result(u)
                 norm, sum_p2, max_p, argmax = ex.result_stats()
             exponent = ex.get_exponent()[0] if strip_exponent else 0.0
+            self._reusable = (st, bool(strip_exponent))
         shape = tuple(self.tree.gathered_shape())
         coords = np.stack(np.unravel_index(idx, shape), axis=1).astype(np.int64) if shape else np.zeros((idx.size, 0), np.int64)
         return SampleResult(indices=idx, coords=coords, amplitudes=amps, p=p, norm=norm, sum_p2=sum_p2, max_p=max_p,
                             argmax=argmax, exponent=exponent)
+
+    # ---- top-k and marginals of the result on the device (csrc/ctg_reduce.hip) ------------------ #
+
+    def _reduce_state(self, arrays, strip_exponent, check_zero, reuse):
+        """Under the lock: the executor state whose result tensor holds the whole contraction, and whether it was
+        run under ``strip_exponent`` -- contracted now from ``arrays``, or (``reuse``) left by the call before."""
+        if reuse:
+            if self._reusable is None:
+                raise RuntimeError("reuse=True: the call made last on this contractor left no result to read "
+                                   "(none was made, or another call -- audit, vjp, contract_slice, ... -- came between).")
+            st, strip = self._reusable
+            if not getattr(st["exec"], "handle", None):
+                self._reusable = None
+                raise RuntimeError("reuse=True: the executor that held the result has been released.")
+            return st, strip
+        st = self.setup(*arrays)
+        ex = st["exec"]
+        self._choose_arithmetic(ex)
+        ex.set_strip_exponent(strip_exponent, check_zero)
+        ex.zero_result()
+        self.run_share(ex, 0, 1, False)
+        self._reusable = (st, bool(strip_exponent))
+        return st, bool(strip_exponent)
+
+    def topk(self, *arrays, k, strip_exponent=False, check_zero=False, reuse=False):
+        """Contract (all slices, as a call does) and return the ``k`` most probable members of the result --
+        ``p = |x|^2`` descending, the lower flat index first among equal ``p``, exactly numpy's
+        ``lexsort((index, -p))[:k]`` -- selected on the device; the result tensor is never copied to the host
+        (``ctg_exec_result_topk``).  Returns a :class:`TopKResult`.  With
+        ``strip_exponent`` the amplitudes, ``p``, ``norm`` and ``sum_p2`` are the mantissa's.  ``reuse=True``
+        (no arrays): read the result tensor left by the call made directly before on this contractor
+        (``__call__``, ``sample``, ``topk`` or ``marginal``; its ``strip_exponent`` applies) instead of
+        contracting again; ``RuntimeError`` when there is none or another call came between.  ``ValueError`` for
+        ``k < 1`` or above the number of elements or 2^20, and when the result holds a NaN or inf.  An all-zero
+        result is no error.  Not differentiable."""
+        k = runtime.check_topk_k(k)
+        n = prod(self.tree.gathered_shape())
+        if k > n or k > runtime.Executor.TOPK_MAX:
+            raise ValueError(f"k = {k}: the result has {n} elements and at most {runtime.Executor.TOPK_MAX} are returned.")
+        if reuse and arrays:
+            raise ValueError("reuse=True reads the result of the call before: give no arrays.")
+        with self._lock:
+            st, strip = self._reduce_state(arrays, strip_exponent, check_zero, reuse)
+            ex = st["exec"]
+            idx, amps, p = ex.topk_result(k)
+            norm, sum_p2 = ex.sample_info()[:2]   # (of the statistics passes the call just ran)
+            exponent = ex.get_exponent()[0] if strip else 0.0
+        shape = tuple(self.tree.gathered_shape())
+        coords = np.stack(np.unravel_index(idx, shape), axis=1).astype(np.int64) if shape else np.zeros((idx.size, 0), np.int64)
+        return TopKResult(indices=idx, coords=coords, amplitudes=amps, p=p, norm=norm, sum_p2=sum_p2, exponent=exponent)
+
+    def marginal(self, *arrays, keep, strip_exponent=False, check_zero=False, reuse=False):
+        """Contract (all slices, as a call does) and return the marginal of ``p = |x|^2`` over the output indices
+        ``keep`` -- ``p`` summed over every other output index, in double with a fixed order, on the device
+        (``ctg_exec_result_marginal``).  ``keep``: a sequence of output index labels, or
+        a list of such sequences (several marginals of one contraction; ``p`` is a list then).  The axes of an
+        array are in the order the labels were named; an output index projected onto one value keeps its size-1
+        axis; no label: a 0-d array, ``sum p``.  Returns a :class:`MarginalResult`.  ``ValueError`` -- before the
+        device is touched -- for a label that is unknown, not an output index, or repeated.  ``reuse=True``: as
+        for :meth:`topk`.  Not differentiable."""
+        several, reqs = _marginal_requests(self.tree, keep)
+        if reuse and arrays:
+            raise ValueError("reuse=True reads the result of the call before: give no arrays.")
+        shape = tuple(self.tree.gathered_shape())
+        with self._lock:
+            st, strip = self._reduce_state(arrays, strip_exponent, check_zero, reuse)
+            ex = st["exec"]
+            outs = []
+            for labels, flags, kshape, perm in reqs:
+                flat = ex.marginal_result(shape, flags)
+                outs.append(np.array(flat.reshape(kshape).transpose(perm), order="C"))   # (0-d for no label)
+            norm = ex.sample_info()[0]
+            exponent = ex.get_exponent()[0] if strip else 0.0
+        return MarginalResult(p=outs if several else outs[0], norm=norm, exponent=exponent)
 
     def profile(self, arrays, slice_id=0):
         """Per-step milliseconds for one slice (see ``Plan.describe_steps``)."""
@@ -739,6 +865,7 @@ class HipContractor:
 
     def close(self):
         with self._lock:
+            self._reusable = None
             for st in self._execs.values():
                 st["exec"].close()
             self._execs.clear()

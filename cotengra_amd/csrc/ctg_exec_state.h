@@ -159,6 +159,11 @@ struct ctg_exec {
     // sums of squares | the pass's per-workgroup rows] -- allocated by the first call, grown on demand
     void* d_range = nullptr;
     int64_t range_bytes = 0;
+    // top-k and marginals of the result tensor (ctg_reduce.hip): digit counts, block counts and their scans, the
+    // compact key list and the k records / the output and the partial sums of a slab -- allocated by the first call,
+    // grown on demand
+    void* d_reduce = nullptr;
+    int64_t reduce_bytes = 0;
 };
 
 

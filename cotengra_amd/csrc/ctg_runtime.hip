@@ -1812,6 +1812,7 @@ int ctg_exec_destroy(ctg_exec* e) {
     if (e->d_sample_blocks) (void)hipFree(e->d_sample_blocks);
     if (e->d_sample_io) (void)hipFree(e->d_sample_io);
     if (e->d_range) (void)hipFree(e->d_range);
+    if (e->d_reduce) (void)hipFree(e->d_reduce);
     for (hipEvent_t ev : e->sample_ev)
         if (ev) (void)hipEventDestroy(ev);
     delete e;
@@ -2428,6 +2429,7 @@ int ctg_exec_device_bytes(ctg_exec* e, int64_t* bytes) {
     if (e->d_scratch) n += e->scratch_total;
     n += e->sample_blocks_bytes + e->sample_io_bytes;   // (ctg_sample.hip: allocated by the first statistics / draw)
     n += e->range_bytes;                                // (ctg_range.hip: allocated by the first range audit)
+    n += e->reduce_bytes;                               // (ctg_reduce.hip: allocated by the first top-k / marginal)
     *bytes = n;
     return CTG_OK;
 }

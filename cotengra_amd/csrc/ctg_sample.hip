@@ -27,66 +27,15 @@
 #include <cstring>
 
 #include "ctg_exec_state.h"
+#include "ctg_sample_elem.h"
 
 namespace ctg {
 
-constexpr int kSampleBlock = 4096;        // elements per block of pass 1 (B)
-constexpr int kSampleThreads = 256;
 constexpr int kSampleRun = kSampleBlock / 64;   // contiguous elements per lane in sample_kernel
 constexpr int kScanThreads = 1024;
 constexpr int64_t kSampleChunk = 1 << 18; // draws per launch of sample_kernel
 
-// p of one element: products and sum each rounded once, never fused with each other or with the sum p goes into
-// (what a host reference computes, and the same value wherever a kernel forms it)
-template <typename T> struct SampleElem;
-template <> struct SampleElem<float> {
-    static __device__ __forceinline__ double p(float x) {
-#pragma clang fp contract(off)
-        const double a = (double)x * (double)x;
-        return a;
-    }
-};
-template <> struct SampleElem<double> {
-    static __device__ __forceinline__ double p(double x) {
-#pragma clang fp contract(off)
-        const double a = x * x;
-        return a;
-    }
-};
-template <> struct SampleElem<float2> {
-    static __device__ __forceinline__ double p(float2 x) {
-#pragma clang fp contract(off)
-        const double a = (double)x.x * (double)x.x, b = (double)x.y * (double)x.y;
-        return a + b;
-    }
-};
-template <> struct SampleElem<double2> {
-    static __device__ __forceinline__ double p(double2 x) {
-#pragma clang fp contract(off)
-        const double a = x.x * x.x, b = x.y * x.y;
-        return a + b;
-    }
-};
-
-// p of the V = 16 / sizeof(T) elements from e on (e a multiple of V); elements at or past n count as 0.
-// `vec`: x is 16-byte aligned (one 16-byte load where the group lies inside the tensor).
-template <typename T>
-__device__ __forceinline__ void load_group_p(const T* __restrict__ x, int64_t e, int64_t n, bool vec,
-                                             double (&p)[16 / sizeof(T)]) {
-    constexpr int V = 16 / sizeof(T);
-    if (vec && e + V <= n) {
-        union {
-            uint4 raw;
-            T v[V];
-        } g;
-        g.raw = *reinterpret_cast<const uint4*>(x + e);
-#pragma unroll
-        for (int k = 0; k < V; ++k) p[k] = SampleElem<T>::p(g.v[k]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < V; ++k) p[k] = (e + k < n) ? SampleElem<T>::p(x[e + k]) : 0.0;
-    }
-}
+// (kSampleBlock, kSampleThreads, SampleElem<T>::p and load_group_p: ctg_sample_elem.h, shared with ctg_reduce.hip)
 
 // (m, i) <- the larger p, the lower index among equals
 __device__ __forceinline__ void max_merge(double& m, int64_t& i, double mo, int64_t io) {

@@ -202,6 +202,31 @@ class ContractExpression:
             _close_all(victims)
         return out
 
+    def _after_reduce(self):
+        if self._cached:
+            self._bytes = self.device_bytes()   # (the scratch of the kernels is counted from here on)
+            with _EXPR_LOCK:
+                victims = _trim_expression_cache(keep=self)
+            _close_all(victims)
+
+    def topk(self, *arrays, k, **kwargs):
+        """``expr(*arrays)`` followed by the ``k`` most probable members of ``|result|^2``, selected on the device
+        (``HipContractor.topk``); the expression's own ``strip_exponent`` / ``check_zero`` unless given."""
+        kwargs.setdefault("strip_exponent", self.fn.strip_exponent)
+        kwargs.setdefault("check_zero", self.fn.check_zero)
+        out = self.fn.topk(*arrays, k=k, **kwargs)
+        self._after_reduce()
+        return out
+
+    def marginal(self, *arrays, keep, **kwargs):
+        """``expr(*arrays)`` followed by the marginal of ``|result|^2`` over the output indices ``keep`` on the
+        device (``HipContractor.marginal``); the expression's own ``strip_exponent`` / ``check_zero`` unless given."""
+        kwargs.setdefault("strip_exponent", self.fn.strip_exponent)
+        kwargs.setdefault("check_zero", self.fn.check_zero)
+        out = self.fn.marginal(*arrays, keep=keep, **kwargs)
+        self._after_reduce()
+        return out
+
     def device_bytes(self):
         """Device memory this expression's executors hold right now (``ctg_exec_device_bytes``:
         arena x slice batch, inputs, tables, result, scratch), read under the contractor's lock

@@ -48,6 +48,8 @@ SYMBOLS = (
     "ctg_exec_sample_result",
     "ctg_exec_sample_info",
     "ctg_exec_range_audit",
+    "ctg_exec_result_topk",
+    "ctg_exec_result_marginal",
     "ctg_exec_download_result",
     "ctg_exec_download_arena",
     "ctg_exec_get_state",
@@ -161,6 +163,8 @@ def load():
         "ctg_exec_sample_info": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), i64p,
                                  C.POINTER(C.c_float)],
         "ctg_exec_range_audit": [vp, C.c_int64, i64p, C.POINTER(C.c_double)],
+        "ctg_exec_result_topk": [vp, C.c_int64, i64p, vp, C.POINTER(C.c_double)],
+        "ctg_exec_result_marginal": [vp, C.c_int64, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_double)],
         "ctg_exec_download_result": [vp, vp],
         "ctg_exec_download_arena": [vp, C.c_int64, C.c_int64, vp],
         "ctg_exec_get_state": [vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_int)],
@@ -209,6 +213,22 @@ def _check(rc):
 
 def _i64p(arr):
     return arr.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def check_topk_k(k):
+    """``k`` of a top-k request as an int: ``TypeError`` unless it is an integer (bool excluded), ``ValueError``
+    below 1 -- host only, before any device work."""
+    import operator
+
+    if isinstance(k, (bool, np.bool_)):
+        raise TypeError(f"k = {k!r} is not an integer.")
+    try:
+        k = operator.index(k)
+    except TypeError:
+        raise TypeError(f"k = {k!r} is not an integer.") from None
+    if k < 1:
+        raise ValueError(f"k = {k}: need at least 1.")
+    return k
 
 
 class DevicePlan:
@@ -449,6 +469,43 @@ class Executor:
         ms = (C.c_float * 2)()
         _check(load().ctg_exec_sample_info(self.handle, C.byref(s), C.byref(q), C.byref(m), C.byref(i), ms))
         return s.value, q.value, m.value, i.value, (ms[0], ms[1])
+
+    # -- top-k and marginals of the result tensor (csrc/ctg_reduce.hip) -- #
+
+    TOPK_MAX = 1 << 20   # CTG_TOPK_MAX
+
+    def topk_result(self, k):
+        """The ``k`` most probable members of the result tensor (``ctg_exec_result_topk``): ``(flat indices, the
+        elements there, their p)`` in the order ``p`` descending, the lower index first among equal ``p`` -- numpy's
+        ``lexsort((index, -p))[:k]``, exactly.  ``ValueError`` for ``k < 1``, ``k`` above the number of elements or
+        above ``TOPK_MAX`` (nothing is launched) and for a result whose ``sum p`` is not finite."""
+        k = check_topk_k(k)
+        idx = np.empty(k, dtype=np.int64)
+        elems = np.empty(k, dtype=np.dtype(self.plan.dtype))
+        p = np.empty(k, dtype=np.float64)
+        _check(load().ctg_exec_result_topk(self.handle, k, _i64p(idx), C.c_void_p(elems.ctypes.data),
+                                           p.ctypes.data_as(C.POINTER(C.c_double))))
+        return idx, elems, p
+
+    def marginal_result(self, extents, keep):
+        """``out[j] = sum p`` over the elements of the result tensor whose kept coordinates are ``j``
+        (``ctg_exec_result_marginal``): ``extents`` is the shape of the result, ``keep[a]`` 0 or 1 per axis; a flat
+        float64 array, row-major over the kept axes in the tensor's own order.  ``ValueError`` for a wrong product of
+        the extents, a keep entry outside {0, 1} and for a result whose ``sum p`` is not finite."""
+        ext = np.ascontiguousarray(extents, dtype=np.int64).reshape(-1)
+        kp = np.ascontiguousarray(keep, dtype=np.int32).reshape(-1)
+        if ext.size != kp.size:
+            raise ValueError(f"{ext.size} extents and {kp.size} keep entries.")
+        m = 1
+        for d, f in zip(ext.tolist(), kp.tolist()):
+            if d < 1:
+                raise ValueError(f"extent {d} is not positive.")
+            if f == 1:
+                m *= d
+        out = np.empty(m, dtype=np.float64)
+        _check(load().ctg_exec_result_marginal(self.handle, ext.size, _i64p(ext), kp.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
 
     # -- range audit (csrc/ctg_range.hip, cotengra_amd/rangeaudit.py) -- #
 

@@ -1060,6 +1060,23 @@ class ContractionTree:
 
         return _tree_contractor(self, order).sample(*arrays, n_samples=n_samples, **kwargs)
 
+    def contract_topk(self, arrays, k, order=None, **kwargs):
+        """:meth:`contract` followed by the selection of the ``k`` most probable members of the result on the
+        device (``p = |x|^2`` descending, the lower flat index first among equals), the result tensor staying
+        there (``HipContractor.topk``; ``kwargs``: ``strip_exponent``, ``check_zero``, ``reuse``).  Not
+        differentiable."""
+        from .contractor import _tree_contractor
+
+        return _tree_contractor(self, order).topk(*arrays, k=k, **kwargs)
+
+    def contract_marginal(self, arrays, keep, order=None, **kwargs):
+        """:meth:`contract` followed by the marginal of ``|result|^2`` over the output indices ``keep`` (a
+        sequence of labels, or a list of such sequences) on the device (``HipContractor.marginal``; ``kwargs``:
+        ``strip_exponent``, ``check_zero``, ``reuse``).  Not differentiable."""
+        from .contractor import _tree_contractor
+
+        return _tree_contractor(self, order).marginal(*arrays, keep=keep, **kwargs)
+
     def contract_audit(self, arrays, slices=(0,), order=None):
         """Range audit of the contraction on ``arrays`` (``HipContractor.audit``): the
         slices ``slices`` run step by step, one record per plan step with the exponent statistics of its

@@ -250,7 +250,8 @@ int ctg_exec_run_share(ctg_exec* exec, int64_t rank, int64_t world, int64_t unit
 /* ABI 4.  Device memory this executor holds right now: inputs space, arena x slice batch,
  * tables, the result if it owns it, the scratch buffer if the plan has a step that needs one
  * (allocated by ctg_exec_create), the scratch of ctg_exec_result_stats / ctg_exec_sample_result once they
- * have run (ABI 9).  What a cache of contractors -- the reference keeps them
+ * have run (ABI 9), of ctg_exec_range_audit and of ctg_exec_result_topk / ctg_exec_result_marginal likewise
+ * (ABI 10).  What a cache of contractors -- the reference keeps them
  * on the tree, core.py:3708-3722 -- has to count against its budget. */
 int ctg_exec_device_bytes(ctg_exec* exec, int64_t* bytes);
 /* ABI 5.  Is there a kernel instantiation for a three-step tile of this shape (stem steps fused
@@ -366,6 +367,36 @@ int ctg_exec_sample_info(ctg_exec* exec, double* sum_p, double* sum_p2, double* 
  * ctg_exec_destroy. */
 #define CTG_RANGE_WORDS 260
 int ctg_exec_range_audit(ctg_exec* exec, int64_t slice_id, int64_t* rows, double* sumsq);
+/* Added to ABI 10 WITHOUT a bump of CTG_ABI_VERSION (two new symbols, nothing else changes; a binding that needs them
+ * looks them up): the k most probable members, and marginals, of the result tensor on the device
+ * (csrc/ctg_reduce.hip).  Both read the result tensor as ctg_exec_sample_result does --
+ * result_elems elements, row-major, whoever owns the memory, the mantissa under strip_exponent, after the work already
+ * enqueued on the executor's stream -- with the same p_i = |x_i|^2 in double, and synchronise the stream.  Both return
+ * CTG_E_NORM when sum p (from the statistics passes of ABI 9, which they run first) is not finite: a NaN or inf
+ * member.  An all-zero tensor is NOT an error here.  No floating-point atomics; every grid and every association of a
+ * sum is a function of (result_elems, k) / (extents, keep): the same bytes give the same bits on every run and every
+ * executor.  The scratch is allocated by the first call, grown on demand, counted by ctg_exec_device_bytes and freed
+ * by ctg_exec_destroy.  Not differentiable; no multi-rank entry (as for ABI 9). */
+/* The first k members of the order (p descending, lower flat index first among equal p), in that order: idx[k], and
+ * where non-NULL elems[k] (plan dtype) and p[k].  Exact: numpy's lexsort((index, -p))[:k] index for index, p bit for
+ * bit.  A radix select on the bit pattern of p (12-bit digits; on a compact list of the surviving keys once at most
+ * 2^16 survive), a collection in index order, and the ordering of the k records on the host inside the call.
+ * CTG_E_INVALID for k < 1, k > result_elems, k > CTG_TOPK_MAX or a null exec / idx -- checked on the host before
+ * anything is launched.  Scratch: 16 MiB of digit counts at most, 24 bytes per 4096 elements, 512 KiB, 32 bytes per
+ * record. */
+#define CTG_TOPK_MAX (1 << 20)
+int ctg_exec_result_topk(ctg_exec* exec, int64_t k, int64_t* idx, void* elems, double* p);
+/* out[j] = sum of p over the elements whose kept coordinates are j: extents[rank] is the shape of the result (its
+ * product must equal result_elems), keep[a] in {0, 1} selects the axes kept, out holds prod(kept extents) doubles,
+ * row-major over the kept axes in the tensor's own axis order.  rank = 0 or no kept axis: out[0] = sum p; all axes
+ * kept: out = p.  Every extent a power of two (and at least 4096 elements): per block of 4096 elements a tree over the
+ * dropped bits, then the blocks of an output in ascending order in chunks of 64, the tensor in slabs of at most
+ * CTG_MARGINAL_PARTIALS partial sums; any other shape: a serial walk per (output, chunk of 1024 complement positions).
+ * |out[j] - exact| <= (t - 1) 2^-53 out[j] for the t elements of an output.  CTG_E_INVALID for a negative rank, a
+ * non-positive extent, a wrong product, a keep value outside {0, 1} or null pointers.  Scratch: 8 bytes per output
+ * and at most 2 * 8 * CTG_MARGINAL_PARTIALS bytes (general route: 8 bytes per 512 elements instead). */
+#define CTG_MARGINAL_PARTIALS (1 << 22)
+int ctg_exec_result_marginal(ctg_exec* exec, int64_t rank, const int64_t* extents, const int32_t* keep, double* out);
 /* debugging aid: copy `n` elements of the arena starting at element `offset`
  * to the host (synchronous) */
 int ctg_exec_download_arena(ctg_exec* exec, int64_t offset, int64_t n, void* host_out);
