@@ -459,6 +459,24 @@ __device__ __forceinline__ void settle(T& v) {
 #ifndef CTG_STEM_DEPTH
 #define CTG_STEM_DEPTH 2
 #endif
+// How the 16-bit kernels issue their memory instructions (profiles/stem_mempath_probe.txt, profiles/stem_mempath.txt;
+// DESIGN 4.2).  No switch changes which products an accumulator sees or their order: results are bit-identical either
+// way.  GATHER_PORTIONS = 0 and NT_STORES = 0 rebuild the issue order and cache policy of the kernels before them
+// (tools/build_variants.py).
+// GATHER_PORTIONS (on): the four fire2 of the task two ahead go out one or two in front of each product of the task being
+// multiplied, not back to back behind the split (all four register pairs are free once the split has read them).
+// NT_STORES (on): the result's stores carry the non-temporal hint (plain C++: __builtin_nontemporal_store).  Measured on
+// results of gigabytes; not measured on results small enough to stay cached until the next launch reads them.
+// (Measured and not kept: a consumer's pending 16 stores handed out between the chunk multiplications of its next item
+// instead of in one drain at the item's head -- +0.1, -1.1 and +0.4 ms per slice at spreads of 0.1-0.3.)
+#ifndef CTG_STEM_GATHER_PORTIONS
+#define CTG_STEM_GATHER_PORTIONS 1
+#endif
+#ifndef CTG_STEM_NT_STORES
+#define CTG_STEM_NT_STORES 1
+#endif
+constexpr bool STEM_NT_STORES = CTG_STEM_NT_STORES != 0;
+constexpr bool STEM_GATHER_PORTIONS = CTG_STEM_GATHER_PORTIONS != 0;
 // AR: the arithmetic of the BF3 = true kernels (Bf16x3 / Fp16x2 above); the body of stem2_kernel / stem2h_kernel below.
 template <class AR, bool PACK1, bool PACK2, int RT1_, int CS1, int NCH, int IT2_, bool BR1, int K2Q, bool VEC, bool BF3,
           bool RI2, bool ONE, int ITM, bool PACKM, bool XM, bool LM, bool WS>
@@ -939,7 +957,12 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
             return;
         }
 #endif
-        *(float2*)q = v;
+        if constexpr (STEM_NT_STORES) {
+            typedef float f32x2 __attribute__((ext_vector_type(2)));
+            __builtin_nontemporal_store(f32x2{v.x, v.y}, (f32x2*)q);
+        } else {
+            *(float2*)q = v;
+        }
     };
     // stores lo .. hi - 1 of the pending item.  set_tag: which accumulator set holds it (RI2);
     // scaled_tag: a strip_exponent run (RI2 scales at the store; the X / Y form scaled its copy)
@@ -978,8 +1001,13 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
             AR::split(re, r3, h2_sa);
             AR::split(im, i3, h2_sa);
             __builtin_amdgcn_sched_barrier(0);
+            // (the split has read all eight elements: every register pair may be refilled from here on; in portions
+            // where the refill is unconditional -- the static kernels -- so that the products stay one block)
+            constexpr bool GP = STEM_GATHER_PORTIONS && decltype(always_tag)::value;
+            if constexpr (!GP) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) fire2(r, q, base, always_tag);
+                for (int q = 0; q < 4; ++q) fire2(r, q, base, always_tag);
+            }
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 if (!PACK1 && !XM1) n3[q] = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, i3[q]) ^ 0x80008000u);
@@ -1004,6 +1032,14 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
 #pragma unroll
             for (int t = 0; t < 6; t += AR::t_step(t)) {
                 const int ta = bf3_ta(t), tb = bf3_tb(t);
+                if constexpr (GP) {
+                    // product i of P refills the pairs ceil(4 i / P) .. ceil(4 (i + 1) / P) - 1, in front of its
+                    // MFMAs: 2, 1, 1 (three products) or 1, 1, 0, 1, 1, 0 (six) -- the same sequence for every task
+                    constexpr int P = AR::products;
+                    const int i = AR::t_index(t);
+#pragma unroll
+                    for (int q = (4 * i + P - 1) / P; q < (4 * (i + 1) + P - 1) / P; ++q) fire2(r, q, base, always_tag);
+                }
                 if (PACK1) {
                     ax[m] = AR::mfma(r3[ta], bp3[0][tb], (fresh && t == 0) ? zero16 : ax[m]);
                     ax[m] = AR::mfma(i3[ta], bq3[0][tb], ax[m]);

@@ -4,6 +4,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -shared -fPIC -o libctg_probe.so ctg_probe.hip
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -285,4 +286,158 @@ extern "C" double ctg_probe_valu(int which, int blocks, int iters, void* out, vo
     if (which == 0) hipLaunchKernelGGL((valu_rate_kernel<double, 16>), dim3(blocks), dim3(256), 0, s, (double*)out, iters);
     else hipLaunchKernelGGL((valu_rate_kernel<float, 16>), dim3(blocks), dim3(256), 0, s, (float*)out, iters);
     return 2.0 * 16 * (double)iters * 256.0 * blocks;
+}
+
+// ---- one stem workgroup (profiles/stem_mempath_probe.txt) ------------------------------------- //
+// The memory path of a specialised-wave stem pair without its arithmetic: one workgroup of 8 waves per CU,
+// persistent over tiles.  Waves 0-3 gather: 4 KB tasks of eight 8-byte-per-lane loads over 128-byte runs
+// (runs of 32 tasks interleave), GD tasks in flight, four tasks per tile; a task's registers are summed (the
+// split's read of all eight), then refilled for the task GD ahead between four groups of nm dependent MFMAs.
+// Waves 4-7 store: two 8 KB items per tile as sixteen 8-byte-per-lane stores in 256-byte runs (runs of 16
+// items interleave), each item behind eight groups of 2 nm MFMAs; the first item's stores go out between
+// the groups of the second, the second's between the tile's two barriers.  A tile moves 64 KB in and 64 KB out.
+//   GF: fire2-equivalents (two loads) issued at a time: 4 = all behind the sum, 2 = groups 0 and 2, 1 = one per group
+//   SP: stores at a time: 16 = all at the item's head, 8 = groups 0 and 4, 4 = every second group, 2 = every group
+//   NTL / NTS: non-temporal loads / stores;  skew: workgroup b starts (b & 7) * skew / 8 ticks of the 100 MHz wall clock late
+typedef float f32x16w __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8w __attribute__((ext_vector_type(8)));
+
+template <int GF, int SP, int GD, bool NTL, bool NTS>
+__global__ __launch_bounds__(512, 1) void stemwg_kernel(const f32x2* __restrict__ src, f32x2* __restrict__ dst,
+                                                        int64_t n_tiles, int nm, int skew) {
+    __shared__ float mid[4][16][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t tile0 = blockIdx.x, step = gridDim.x;
+    const int64_t mine = (n_tiles - tile0 + step - 1) / step;   // >= 1: grid <= n_tiles
+    const int64_t last_tile = tile0 + (mine - 1) * step;
+    if (skew > 0) {
+        const long long t0 = (long long)wall_clock64(), d = (long long)skew * (blockIdx.x & 7) / 8;
+        while ((long long)wall_clock64() - t0 < d) __builtin_amdgcn_s_sleep(1);
+    }
+    f32x16w acc;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) acc[t] = 0.f;
+    const unsigned bb = 0x3f803f80u + lane;
+    const bf16x8w b = __builtin_bit_cast(bf16x8w, u32x4p{bb, bb, bb, bb});
+    auto mfmas = [&](float x, int n) __attribute__((always_inline)) {
+        const unsigned u = __builtin_bit_cast(unsigned, x);
+        const bf16x8w a = __builtin_bit_cast(bf16x8w, u32x4p{u, u, u, u});
+        for (int i = 0; i < n; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    if (w < 4) {
+        f32x2 r[GD][8];
+        // loads 2 q, 2 q + 1 of task s of this wave (s counts its tasks over all its tiles; past the end: the last tile again)
+        auto fire2 = [&](f32x2 (&x)[8], int64_t s, int q) __attribute__((always_inline)) {
+            int64_t tile = tile0 + (s >> 2) * step;
+            tile = tile < last_tile ? tile : last_tile;
+            const int64_t task = (tile * 4 + w) * 4 + (s & 3);
+            const f32x2* base = src + (task >> 5) * 16384 + (task & 31) * 16 + (lane & 15);
+#pragma unroll
+            for (int j = 2 * q; j < 2 * q + 2; ++j) {
+                const f32x2* p = base + (j * 4 + (lane >> 4)) * 512;
+                x[j] = NTL ? __builtin_nontemporal_load(p) : *p;
+            }
+        };
+        auto consume = [&](f32x2 (&x)[8], int64_t s) __attribute__((always_inline)) {
+            float v = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v += x[j][0] + x[j][1];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                if (GF == 4 && g == 0)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) fire2(x, s + GD, q);
+                if (GF == 2 && (g & 1) == 0) {
+                    fire2(x, s + GD, g);
+                    fire2(x, s + GD, g + 1);
+                }
+                if (GF == 1) fire2(x, s + GD, g);
+                __builtin_amdgcn_sched_barrier(0);
+                mfmas(v, nm);
+            }
+        };
+#pragma unroll
+        for (int g = 0; g < GD; ++g)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) fire2(r[g], g, q);
+        auto tile = [&](int64_t t) __attribute__((always_inline)) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) consume(r[k & (GD - 1)], 4 * t + k);
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < 16; ++i) mid[w][i][lane] = acc[i];   // the scatter's stand-in
+            __syncthreads();
+        };
+        // (first tile peeled, here and below: the waits at the loop header then count what the steady state has in flight)
+        tile(0);
+        for (int64_t t = 1; t < mine; ++t) tile(t);
+        if (acc[0] == 12345.678f) dst[lane] = f32x2{acc[1], acc[2]};
+    } else {
+        const int cw = w - 4;
+        f32x2 pv[16];
+        f32x2* pdst = dst;
+        auto drain = [&](int lo, int hi) __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = lo; i < hi; ++i) {
+                f32x2* q = pdst + (i * 2 + (lane >> 5)) * 512;
+                if (NTS) __builtin_nontemporal_store(pv[i], q);
+                else *q = pv[i];
+            }
+        };
+        auto item = [&](int64_t tile, int it, float v, auto pending_tag) __attribute__((always_inline)) {
+            constexpr bool PENDING = decltype(pending_tag)::value;
+#pragma unroll
+            for (int g = 0; g < 8; ++g) {
+                if constexpr (PENDING) {
+                    constexpr int EVERY = SP / 2;   // a portion of SP stores in front of every EVERY-th group
+                    if (g % EVERY == 0) drain(g / EVERY * SP, (g / EVERY + 1) * SP);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                mfmas(v, 2 * nm);
+            }
+            const int64_t id = (tile * 4 + cw) * 2 + it;
+            pdst = dst + (id >> 4) * 16384 + (id & 15) * 32 + (lane & 31);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) pv[i] = f32x2{acc[i], acc[i] + 1.f};
+        };
+        auto tile = [&](int64_t t, auto first_tag) __attribute__((always_inline)) {
+            __syncthreads();
+            if constexpr (!decltype(first_tag)::value) drain(0, 16);   // the last item's stores: while the gather waves scatter
+            __syncthreads();
+            const float v = mid[cw][0][lane];
+            item(tile0 + t * step, 0, v, std::false_type{});
+            item(tile0 + t * step, 1, v, std::true_type{});
+        };
+        tile(0, std::true_type{});
+        for (int64_t t = 1; t < mine; ++t) tile(t, std::false_type{});
+        drain(0, 16);
+    }
+}
+
+// nbytes: size of src and of dst, a multiple of 128 KB (two tiles: the interleaved regions are whole); nt: bit 0 =
+// non-temporal loads, bit 1 = non-temporal stores.  Returns 0, -1 (no such variant), -2 (size) or the HIP error.
+extern "C" int ctg_probe_stemwg(const void* src, void* dst, int64_t nbytes, int gf, int sp, int gd, int nt, int nm, int skew,
+                                int blocks, void* stream) {
+    if (nbytes <= 0 || nbytes % 131072 != 0) return -2;
+    const int64_t n_tiles = nbytes / 65536;
+    if (blocks < 1 || blocks > n_tiles || nm < 0 || skew < 0) return -2;
+    hipStream_t s = (hipStream_t)stream;
+    bool done = false;
+#define TRY(GF_, SP_, GD_, NT_)                                                                                              \
+    if (!done && gf == GF_ && sp == SP_ && gd == GD_ && nt == NT_) {                                                         \
+        hipLaunchKernelGGL((stemwg_kernel<GF_, SP_, GD_, (NT_ & 1) != 0, (NT_ & 2) != 0>), dim3((unsigned)blocks), dim3(512), \
+                           0, s, (const f32x2*)src, (f32x2*)dst, n_tiles, nm, skew);                                         \
+        done = true;                                                                                                         \
+    }
+#define TRY_SP(GF_, GD_, NT_) TRY(GF_, 16, GD_, NT_) TRY(GF_, 8, GD_, NT_) TRY(GF_, 4, GD_, NT_) TRY(GF_, 2, GD_, NT_)
+    TRY_SP(4, 2, 0) TRY_SP(2, 2, 0) TRY_SP(1, 2, 0)
+    TRY(4, 16, 4, 0) TRY(1, 2, 4, 0)
+    TRY(4, 16, 2, 1) TRY(4, 16, 2, 2) TRY(4, 16, 2, 3)
+    TRY(1, 2, 2, 1) TRY(1, 2, 2, 2) TRY(1, 2, 2, 3)
+#undef TRY_SP
+#undef TRY
+    if (!done) return -1;
+    return (int)hipGetLastError();
 }
