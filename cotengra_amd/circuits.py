@@ -319,6 +319,42 @@ def top_chaotic(n, gates, marginal_qubits, bunches=1, top=1, seed=None, optimize
     return out
 
 
+def amplitudes_of(n, gates, bitstrings, optimize="greedy", dtype="complex64", target_size=None):
+    """Ideal amplitudes of given bitstrings -- measured or spoofed ones to be scored -- of the ``n``-qubit circuit
+    ``gates``: the qubits on which all ``bitstrings`` agree are projected, the others left open, and of that one
+    network's batch of ``2^k`` amplitudes only the requested members are contracted
+    (``ContractionTree.contract_pick``: a sparse root step, the batch itself never exists).  One network, one
+    tree (``optimize``: as for ``array_contract_tree``; ``target_size`` slices inner indices of the tree found),
+    one call.
+
+    Returns a dict: ``bitstrings`` (as given), ``amplitudes`` (one per bitstring, in that order), ``p`` (their
+    ``|amplitude|^2``, float64) and ``open_qubits`` (the qubits left open, ascending).
+
+    >>> out = amplitudes_of(n, gates, measured)
+    >>> fidelity = linear_xeb(n, out["p"])
+    """
+    from .interface import array_contract_tree
+
+    bitstrings = [str(b) for b in bitstrings]
+    if not bitstrings:
+        raise ValueError("amplitudes_of: no bitstrings.")
+    for b in bitstrings:
+        if len(b) != n or set(b) - {"0", "1"}:
+            raise ValueError(f"amplitudes_of: {b!r} is not a string of {n} characters '0' / '1'.")
+    bits = np.array([[int(c) for c in b] for b in bitstrings], dtype=np.int64)
+    open_qubits = [q for q in range(n) if bits[:, q].min() != bits[:, q].max()]
+    template = "".join("?" if q in open_qubits else bitstrings[0][q] for q in range(n))
+    inputs, output, size_dict, arrays = circuit_to_network(n, gates, template, simplify=True, dtype=dtype)
+    tree = array_contract_tree(inputs, output, size_dict, optimize=optimize)
+    if [tuple(t) for t in tree.inputs] != [tuple(t) for t in inputs] or tuple(tree.output) != tuple(output):
+        raise ValueError("optimize: the tree is not over this circuit's network.")
+    if target_size is not None:
+        tree = tree.slice(target_size=target_size, allow_outer=False)
+    amps = np.asarray(tree.contract_pick(arrays, coords=bits[:, open_qubits]))
+    return {"bitstrings": bitstrings, "amplitudes": amps, "p": np.abs(amps).astype(np.float64) ** 2,
+            "open_qubits": open_qubits}
+
+
 def linear_xeb(n_qubits, probabilities):
     """Linear cross-entropy benchmark fidelity of sampled bitstrings with ideal probabilities
     ``probabilities``: ``2^n mean(p) - 1`` (1 for draws from a Porter-Thomas distribution, 0 for uniform

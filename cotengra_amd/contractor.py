@@ -24,10 +24,15 @@ import threading
 import numpy as np
 
 from . import runtime
-from .plan import DTYPE_CODES, compile_tree
+from .plan import DTYPE_CODES, PICK_MAX, compile_tree
 from .utils import prod
 
 _SUPPORTED = tuple(DTYPE_CODES)
+
+# Held from looking a pick contractor up on its tree until its call has returned, and while one is replaced or
+# closed: no caller runs on a pick contractor that another thread has just closed.  (Taken before, never inside,
+# a contractor's own lock.)
+_PICK_LOCK = threading.RLock()
 
 
 class _Progress:
@@ -270,6 +275,47 @@ def _marginal_requests(tree, keep):
     return several, reqs
 
 
+def pick_requests(tree, coords=None, indices=None):
+    """The request table of ``HipContractor.pick`` as ``(M, len(tree.output))`` int64 coordinates, one column per
+    output index in ``tree.output`` order -- host only.  Exactly one of ``coords`` (that table) and ``indices``
+    (``(M,)`` flat row-major positions in ``tree.gathered_shape()``) is given.  ``ValueError`` for both or
+    neither, a wrong width or dimension, a non-integer dtype, a value outside its extent, more than ``PICK_MAX``
+    requests, and a tree whose output holds a sliced index."""
+    if (coords is None) == (indices is None):
+        raise ValueError("pick: give exactly one of coords and indices.")
+    out_sliced = [ix for ix in tree.output if ix in tree.sliced_inds]
+    if out_sliced:
+        raise ValueError(f"pick: the output indices {out_sliced} of the tree are sliced (projected or not); "
+                         "picking members of a sliced output is not supported -- slice inner indices only.")
+    shape = tuple(int(d) for d in tree.gathered_shape())
+    given = coords if coords is not None else indices
+    if _is_torch(given):
+        given = given.detach().cpu().numpy()
+    given = np.asarray(given)
+    if given.size and not np.issubdtype(given.dtype, np.integer):
+        raise ValueError(f"pick: requests of dtype {given.dtype}; integers are expected.")
+    if coords is not None:
+        if given.ndim != 2 or given.shape[1] != len(shape):
+            raise ValueError(f"pick: coords of shape {given.shape}; expected (M, {len(shape)}), one column per "
+                             f"output index {list(tree.output)}.")
+        req = np.ascontiguousarray(given, dtype=np.int64)
+        for j, (ix, d) in enumerate(zip(tree.output, shape)):
+            if len(req) and (req[:, j].min() < 0 or req[:, j].max() >= d):
+                raise ValueError(f"pick: a coordinate of output index {ix!r} lies outside [0, {d}).")
+    else:
+        if given.ndim != 1:
+            raise ValueError(f"pick: indices of shape {given.shape}; expected (M,).")
+        n = prod(shape)
+        flat = np.ascontiguousarray(given, dtype=np.int64)
+        if len(flat) and (flat.min() < 0 or flat.max() >= n):
+            raise ValueError(f"pick: an index lies outside [0, {n}), the elements of the result.")
+        req = (np.stack(np.unravel_index(flat, shape), axis=1).astype(np.int64) if shape
+               else np.zeros((len(flat), 0), dtype=np.int64))
+    if len(req) > PICK_MAX:
+        raise ValueError(f"pick: {len(req)} requests; at most {PICK_MAX} are taken by one call.")
+    return req
+
+
 class HipContractor:
     """Callable performing the contraction of ``tree`` on an MI355X.
 
@@ -304,7 +350,13 @@ class HipContractor:
         fuse_min_elems=None,
         stem_bf16x3=None,
         crest_limit=None,
+        pick=None,
     ):
+        # a request table (``pick_requests``): the contractor computes those members of the output only, its
+        # result is the ``(M,)`` vector of them (``HipContractor.pick`` builds and caches such contractors)
+        self._pick = pick
+        # the pick contractor this one built last (``_pick_contractor``): closed with it
+        self._picker = None
         self._origin = tree  # whose ``contraction_cores`` hold this contractor's siblings
         if handle_slicing or not tree.sliced_inds:
             self.tree = tree
@@ -369,6 +421,7 @@ class HipContractor:
             plan = self._host_plans[dtype] = compile_tree(
                 self.tree, dtype, order=self.order, force_kernel=self.force_kernel,
                 fuse=self.fuse, fuse_min_elems=self.fuse_min_elems, stem_bf16x3=self.stem_bf16x3,
+                **({} if self._pick is None else {"pick": self._pick}),
             )
             return plan
 
@@ -783,6 +836,62 @@ class HipContractor:
         return SampleResult(indices=idx, coords=coords, amplitudes=amps, p=p, norm=norm, sum_p2=sum_p2, max_p=max_p,
                             argmax=argmax, exponent=exponent)
 
+    # ---- chosen members of the output: a sparse root step (csrc/ctg_pick.hip) -------------------- #
+
+    def _pick_contractor(self, req):
+        """The contractor of the request table ``req``, cached on the tree under ``("hip-pick", order, sha1 of
+        the int64 coords)``; it replaces -- and closes -- the pick contractor cached before it (its tables cost
+        24 bytes per request and plan on the device, and there is no reason to keep many).  Under ``_PICK_LOCK``,
+        which the caller keeps until the call on the returned contractor is over.  The contractor lives until
+        another table replaces it or the contractor that built it is closed."""
+        import hashlib
+
+        cores = self._origin.contraction_cores
+        order = self.order if not callable(self.order) else id(self.order)
+        key = ("hip-pick", order, hashlib.sha1(np.ascontiguousarray(req, dtype=np.int64).tobytes()).hexdigest())
+        fn = cores.get(key)
+        if fn is not None and fn.tree is self.tree:
+            return fn
+        for k in [k for k in cores if isinstance(k, tuple) and k and k[0] == "hip-pick"]:
+            cores.pop(k).close()
+        arith = "auto" if self.auto_arith else (self.stem_arith if self.stem_arith is not None else self.stem_bf16x3)
+        fn = cores[key] = HipContractor(
+            self.tree, order=self.order, handle_slicing=True, device=self.device, force_kernel=self.force_kernel,
+            fuse=self.fuse, fuse_min_elems=self.fuse_min_elems, stem_bf16x3=arith, crest_limit=self.crest_limit,
+            pick=req,
+        )
+        self._picker = fn
+        return fn
+
+    def pick(self, *arrays, coords=None, indices=None, strip_exponent=False, check_zero=False):
+        """Contract (all slices, as a call does) only the requested members of the output: ``coords``, ``(M,
+        len(tree.output))`` integers, one column per output index in ``tree.output`` order, or ``indices``,
+        ``(M,)`` flat row-major positions in ``tree.gathered_shape()`` -- the two forms ``SampleResult`` and
+        ``TopKResult`` carry.  Duplicates are allowed, the order is kept.  Everything below the root of the tree
+        runs as usual; the root is one sparse step whose cost follows ``M``, and the full output tensor never
+        exists (``compile_tree(pick=...)``).  Returns the ``(M,)`` array of amplitudes in
+        the result dtype (a torch tensor for ROCm torch inputs); with ``strip_exponent`` ``(mantissa,
+        exponent)`` as a call does.  ``M = 0``: an empty array, the device is not touched.  ``ValueError`` --
+        before the device is touched -- for what :func:`pick_requests` refuses.  The result tensor of this
+        contractor is not touched, but ``reuse=True`` of :meth:`topk` / :meth:`marginal` refuses to read it after
+        a pick.  Not differentiable."""
+        req = pick_requests(self.tree, coords, indices)
+        with self._lock:
+            self._reusable = None
+        if len(req) == 0:
+            dtype = _result_dtype(arrays) if arrays else "complex64"
+            torch_in = [x for x in arrays if _is_torch(x) and x.is_cuda]
+            if torch_in:
+                import torch
+
+                out = torch.zeros((0,), dtype=getattr(torch, dtype), device=torch_in[0].device)
+            else:
+                out = np.zeros((0,), dtype=dtype)
+            return (out, float("-inf")) if strip_exponent else out
+        with _PICK_LOCK:
+            fn = self._pick_contractor(req)
+            return fn._contract(arrays, False, check_zero, strip_exponent)
+
     # ---- top-k and marginals of the result on the device (csrc/ctg_reduce.hip, DESIGN 12) ------------------ #
 
     def _reduce_state(self, arrays, strip_exponent, check_zero, reuse):
@@ -864,6 +973,13 @@ class HipContractor:
             return st["plan"], st["exec"].profile_slice(slice_id)
 
     def close(self):
+        with _PICK_LOCK:
+            fn, self._picker = self._picker, None
+            if fn is not None:
+                cores = getattr(self._origin, "contraction_cores", None) or {}
+                for k in [k for k, v in cores.items() if v is fn]:
+                    del cores[k]
+                fn.close()
         with self._lock:
             self._reusable = None
             for st in self._execs.values():

@@ -93,7 +93,10 @@ enum StemTab {
     ST_GA_HI = 0, ST_GA_LO, ST_GC_HI, ST_GC_LO, ST_KJ_A, ST_LANE_A, ST_RT_A, ST_CHUNK_A,
     ST_B1_OFF, ST_B2_OFF, ST_MID_ROW, ST_MID_COL, ST_OUT_ROW, ST_OUT_COL, ST_COUNT
 };
-enum Kernel { KERNEL_VALU = 0, KERNEL_MFMA = 1 };
+// KERNEL_PICK (added to ABI 10 without a bump): the sparse root step of a pick plan -- a KIND_PAIR record with
+// N = 1, Bt = 1 and row_lo = 1 whose `hi` row tables hold one offset per requested member of the output
+// (cotengra_amd/plan.py: build_pick_step; kernel: ctg_pick.hip)
+enum Kernel { KERNEL_VALU = 0, KERNEL_MFMA = 1, KERNEL_PICK = 2 };
 enum Space { SPACE_INPUTS = 0, SPACE_ARENA = 1, SPACE_RESULT = 2 };
 
 // Two-level row table: off(i) = hi[i / lo_size] + lo[i % lo_size].
@@ -527,6 +530,18 @@ hipError_t launch_pair_valu_group(int dtype, const ValuGroupItem* d_items, int n
                                   int nz, hipStream_t stream);
 hipError_t launch_pair_mfma(int dtype, const StepArgs& p, const MfmaHints& h, void* scratch,
                             int64_t scratch_bytes, hipStream_t stream);
+// The route of a KERNEL_PICK step of M requests over a contraction of K, the one place that decides it (its
+// mirror for the planner's tests: cotengra_amd/plan.py: pick_route): pair_pick_kernel gives a request at most one
+// wave, so a handful of requests under a very long contraction cannot fill the chip -- those go, unchanged, to
+// launch_pair_valu, whose k-reduction kernels spread K over it (the bounds imply that launcher's own rule,
+// K >= 256 and at most 2^15 outputs).  A function of (M, K) alone.
+constexpr int64_t kPickKredMinK = 1 << 15, kPickKredMaxM = 512;
+inline bool pick_route_kred(int64_t M, int64_t K) { return K >= kPickKredMinK && M <= kPickKredMaxM; }
+// vec: 1 = both operands can be read two adjacent k at a time (decided once per step on the host: MfmaHints::vecA)
+hipError_t launch_pair_pick(int dtype, const StepArgs& p, int vec, void* scratch, int64_t scratch_bytes,
+                            hipStream_t stream);
+// "pair_pick_kernel<T,VEC,SEG>" (T: float, double, c64, c128), or what pair_valu_name says of the k-reduction route
+void pair_pick_name(int dtype, const StepArgs& p, int vec, int64_t scratch_bytes, char* buf, size_t n);
 // Independent small steps of the tiled fast kernel sharing one launch (same tile
 // shape and gather width: `key`); item i owns workgroups [block_begin, +n_blocks).
 struct FastGroupItem {

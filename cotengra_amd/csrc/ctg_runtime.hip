@@ -240,8 +240,16 @@ int validate_plan(ctg_plan* p) {
             if (rc != CTG_OK) return rc;
             continue;
         }
-        if (r[W_KERNEL] < 0 || r[W_KERNEL] > 1)
+        if (r[W_KERNEL] < 0 || r[W_KERNEL] > 2)
             return fail(CTG_E_INVALID, "step %lld: bad kernel", (long long)s);
+        if (r[W_KERNEL] == KERNEL_PICK && (kind != KIND_PAIR || r[W_N] != 1 || r[W_BT] != 1 || r[W_ROW_LO] != 1))
+            return fail(CTG_E_INVALID, "step %lld: the pick kernel executes pair steps with N = 1, Bt = 1 and row_lo = 1 only",
+                        (long long)s);
+        if (r[W_KERNEL] == KERNEL_PICK)   // (pick_vec_ok and the kernel read every table: none may be absent)
+            for (int w : {W_ROWA_HI, W_ROWA_LO, W_ROWB_HI, W_ROWB_LO, W_ROWC_HI, W_ROWC_LO, W_KA_HI, W_KA, W_KB_HI,
+                          W_KB, W_NB, W_NC})
+                if (r[w] < 0)
+                    return fail(CTG_E_INVALID, "step %lld: the pick kernel needs every row, k and n table", (long long)s);
         if (r[W_KERNEL] == KERNEL_MFMA && kind != KIND_PAIR)
             return fail(CTG_E_INVALID, "step %lld: the matrix-core kernels execute pair steps only",
                         (long long)s);
@@ -592,6 +600,24 @@ bool all_even(const ctg_plan* p, int64_t w, int64_t len, int64_t stride = 1) {
     return true;
 }
 
+// A KERNEL_PICK step can read two adjacent k per load (pair_pick_kernel<T, 2, SEG>): the fast level of both k
+// tables is unit-stride and of even length, and every other offset of either operand is even.
+bool pick_vec_ok(const ctg_plan* p, const int64_t* r) {
+    const int64_t k_lo = r[W_K_LO];
+    if ((k_lo & 1) || (r[W_A_OFF] & 1) || (r[W_B_OFF] & 1)) return false;
+    for (int64_t i = 0; i < k_lo; ++i)
+        if (p->tables[r[W_KA] + i] != i || p->tables[r[W_KB] + i] != i) return false;
+    if (!all_even(p, r[W_KA_HI], r[W_K_HI_LEN]) || !all_even(p, r[W_KB_HI], r[W_K_HI_LEN])) return false;
+    if (!all_even(p, r[W_ROWA_HI], r[W_ROW_HI_LEN]) || !all_even(p, r[W_ROWB_HI], r[W_ROW_HI_LEN])) return false;
+    if (!all_even(p, r[W_ROWA_LO], 1) || !all_even(p, r[W_ROWB_LO], 1) || !all_even(p, r[W_NB], 1)) return false;
+    if (p->arena_elems & 1) return false;   // (the replicas of a slice batch)
+    for (int lw : {W_A_LEAF, W_B_LEAF})
+        if (r[lw] >= 0)
+            for (int64_t j = 0; j < p->n_sliced; ++j)
+                if (p->slice_strides[r[lw] * p->n_sliced + j] & 1) return false;
+    return true;
+}
+
 // Build the order tables of one MFMA step; appends to `blob`, returns offsets.
 void build_mfma_order(const ctg_plan* p, const int64_t* r, int bn, int BM,
                       std::vector<uint16_t>& blob, size_t* offA, size_t* offB, int* vecA,
@@ -821,6 +847,7 @@ int build_hints_into(ctg_exec* e, std::vector<MfmaHints>& hints, int64_t zmult,
     std::vector<size_t> offA(p->n_steps, 0), offB(p->n_steps, 0);
     for (int64_t s = 0; s < p->n_steps; ++s) {
         const int64_t* r = &p->steps[s * STEP_WORDS];
+        if (r[W_KIND] == KIND_PAIR && r[W_KERNEL] == KERNEL_PICK) hints[s].vecA = pick_vec_ok(p, r) ? 1 : 0;
         if (r[W_KIND] != KIND_PAIR || r[W_KERNEL] != KERNEL_MFMA) continue;
         MfmaHints& h = hints[s];
         if (p->dtype != CTG_C64) {
@@ -993,6 +1020,7 @@ bool step_needs_scratch(const ctg_exec* e, int64_t s) {
     const ctg_plan* p = e->plan;
     const int64_t* r = &p->steps[s * STEP_WORDS];
     if (r[W_KIND] != KIND_PAIR) return false;
+    if (r[W_KERNEL] == KERNEL_PICK) return pick_route_kred(r[W_R], r[W_K]);
     if (r[W_KERNEL] != KERNEL_MFMA) return !valu_thread_per_output(e->args[s]);
     if (p->dtype != CTG_C64) return false;   // (the real / double kernels have no k-split)
     auto needs = [](const MfmaHints& h) {
@@ -1310,7 +1338,9 @@ int launch_step(ctg_exec* e, int64_t s, hipStream_t stream) {
                         err = launch_pair_mfma(p->dtype, a, h0, e->d_scratch, kScratchBytes, stream);
                     }
                 }
-            } else
+            } else if (r[W_KERNEL] == KERNEL_PICK)
+                err = launch_pair_pick(p->dtype, e->args[s], e->hints[s].vecA, e->d_scratch, kScratchBytes, stream);
+            else
                 err = launch_pair_valu(p->dtype, e->args[s], e->d_scratch, kScratchBytes, stream);
             break;
     }
@@ -1359,6 +1389,7 @@ int build_groups(ctg_exec* e) {
     auto class_of = [&](int64_t s) -> int {
         const int64_t* r = &p->steps[s * STEP_WORDS];
         if (off || r[W_KIND] != KIND_PAIR || e->invariant[s] || lds_member(s)) return -1;
+        if (r[W_KERNEL] == KERNEL_PICK) return -1;   // (its own kernel: never inside a shared launch)
         if (r[W_KERNEL] != KERNEL_MFMA) {
             if (!valu_thread_per_output(e->args[s])) return -1;
             ValuGroupItem it;
@@ -2661,6 +2692,8 @@ int ctg_exec_step_kernel(ctg_exec* e, int64_t step, char* buf, int64_t buflen) {
         h.h2 = pair_step_h2(e, tiled16_step(e, step) && h.splitk <= 1 && !e->grouped[step] &&
                                    e->args[step].zqA <= 1 && e->args[step].zqB <= 1) ? 1 : 0;
         pair_mfma_c64_name(e->args[step], h, kScratchBytes, name, sizeof(name));
+    } else if (r[W_KERNEL] == KERNEL_PICK) {
+        pair_pick_name(p->dtype, e->args[step], e->hints[step].vecA, kScratchBytes, name, sizeof(name));
     } else {
         pair_valu_name(p->dtype, e->args[step], kScratchBytes, name, sizeof(name));
     }

@@ -218,6 +218,14 @@ class ContractExpression:
         self._after_reduce()
         return out
 
+    def pick(self, *arrays, coords=None, indices=None, **kwargs):
+        """Only the requested members of ``expr(*arrays)`` -- ``coords`` ``(M, len(output))`` or ``indices``
+        ``(M,)`` flat positions -- through a sparse root step (``HipContractor.pick``); the expression's own
+        ``strip_exponent`` / ``check_zero`` unless given."""
+        kwargs.setdefault("strip_exponent", self.fn.strip_exponent)
+        kwargs.setdefault("check_zero", self.fn.check_zero)
+        return self.fn.pick(*arrays, coords=coords, indices=indices, **kwargs)
+
     def marginal(self, *arrays, keep, **kwargs):
         """``expr(*arrays)`` followed by the marginal of ``|result|^2`` over the output indices ``keep`` on the
         device (``HipContractor.marginal``); the expression's own ``strip_exponent`` / ``check_zero`` unless given."""
@@ -246,6 +254,7 @@ class ContractExpression:
             fn._lock.release()
 
     def close(self):
+        # (with it goes the pick contractor it built, HipContractor.close)
         self.fn.close()
 
 

@@ -173,13 +173,14 @@ def _simulate(order, kids_of, sizes, root, align, cap):
 CLASS_RANK = {"inv": 0, "group": 1, "slice": 2}
 
 
-def choose_components(tree, dtype, itemsize, node_class, pairs=None):
+def choose_components(tree, dtype, itemsize, node_class, pairs=None, exclude=()):
     """Maximal subtrees of ``tree`` that run LDS-resident.
 
     ``node_class(node)`` -> "inv" | "group" | "slice": how often the step that makes the node's tensor
     runs (once per upload / once per slice group / every slice); for a leaf: the class of its
     preprocessing step (a leaf without one is read straight from the resident inputs and has no class of
-    its own).  The members of a component all have the class of its root ("group" or "slice"); a child of
+    its own).  ``exclude``: nodes that are members of no component (the sparse root step of a pick plan).
+    The members of a component all have the class of its root ("group" or "slice"); a child of
     a lower class is an external operand, gathered from the arena like a leaf is from the inputs.
     Returns a list of :class:`Component`."""
     pairs = pairs or {}
@@ -212,7 +213,7 @@ def choose_components(tree, dtype, itemsize, node_class, pairs=None):
     for p, l, r in topo:
         ok[p] = False
         cls = node_class(p)
-        if cls == "inv" or p in fused:
+        if cls == "inv" or p in fused or p in exclude:
             continue
         l_legs, r_legs, p_legs = tuple(tree.get_legs(l)), tuple(tree.get_legs(r)), legs_of(p)
         o_set, l_set, r_set = set(p_legs), set(l_legs), set(r_legs)

@@ -63,6 +63,8 @@ KIND_STEM2 = 3  # two consecutive pair steps of a stem as one launch (stem.py)
 
 KERNEL_VALU = 0  # one thread per output element, any dtype / any shape
 KERNEL_MFMA = 1  # matrix-core kernels (complex64 on fp32 MFMA, complex128 on fp64 MFMA)
+KERNEL_PICK = 2  # sparse root step: one row per requested member of the output (build_pick_step, csrc/ctg_pick.hip)
+PICK_MAX = 1 << 24  # requests of one pick plan (its three row tables cost 24 bytes each on the device)
 
 SPACE_INPUTS = 0
 SPACE_ARENA = 1
@@ -499,7 +501,7 @@ class Plan:
                 {
                     "step": i,
                     "kind": ("single", "pair", "accum", "stem2")[s.kind],
-                    "kernel": ("valu", "mfma")[s.kernel],
+                    "kernel": ("valu", "mfma", "pick")[s.kernel],
                     "R": s.R,
                     "Bt": s.Bt,
                     "K": s.K,
@@ -742,6 +744,105 @@ def build_single_step(size_dict, src, out_inds, out_ref_factory, node=-1):
 
 
 # --------------------------------------------------------------------------- #
+# sparse root step: only chosen members of the output (compile_tree(pick=...))
+# --------------------------------------------------------------------------- #
+#
+# A request is one position of the tree's output.  The root step of a pick plan is a thread-per-output pair
+# step with N = 1 and row_lo = 1 whose ``hi`` row tables are per-request offsets:
+#
+#     C[rowC(m)] = alpha * sum_k A[rowA(m) + kA(k)] * B[rowB(m) + kB(k)]
+#
+# rowA(m) / rowB(m): the request's coordinates times the operand's strides; rowC(m): the request's position in
+# the caller's table.  The requests are stably sorted by (rowA, rowB), so that consecutive rows share A.
+
+
+# The route of the sparse root step: pair_pick_kernel gives a request at most one wave, so few requests under a
+# very long contraction go to the k-reduction kernels of the thread-per-output route.  The launcher's rule
+# (csrc/ctg_common.h: pick_route_kred, kPickKredMinK / kPickKredMaxM), mirrored here for the planner's tests.
+PICK_KRED_MIN_K = 1 << 15
+PICK_KRED_MAX_M = 512
+
+
+def pick_route(M, K):
+    """``"kred"`` or ``"pick"``: which kernels run a sparse root step of ``M`` requests over a contraction of
+    ``K`` -- a function of ``(M, K)`` alone."""
+    return "kred" if K >= PICK_KRED_MIN_K and M <= PICK_KRED_MAX_M else "pick"
+
+
+def pick_request_rows(out_inds, coords, *operands):
+    """Per-request element offset in each of ``operands``: the sum over the output indices on the operand of
+    ``coord * stride`` -- int64 arrays of ``len(coords)``."""
+    rows = []
+    for t in operands:
+        off = np.zeros(len(coords), dtype=np.int64)
+        for j, ix in enumerate(out_inds):
+            st = t.stride_of(ix)
+            if st:
+                off += coords[:, j] * st
+        rows.append(off)
+    return rows
+
+
+def build_pick_step(size_dict, l, r, out_inds, coords, C, node=-1):
+    """Lower the root einsum ``l, r -> out_inds`` at the requests ``coords`` (``(M, len(out_inds))`` int64) to
+    one PAIR step of kernel ``KERNEL_PICK``; ``C`` is the ``(M,)`` tensor that receives them."""
+    o_set = set(out_inds)
+    if not o_set <= (set(l.inds) | set(r.inds)):
+        raise ValueError(f"Output indices {o_set - (set(l.inds) | set(r.inds))} not found on any input.")
+    A, B = pick_rows_operand(size_dict, l, r, out_inds)
+    a_order, b_order = list(dict.fromkeys(A.inds)), list(dict.fromkeys(B.inds))
+    a_set = set(a_order)
+    # (the contracted group in A's memory order: children laid out for this step -- compile_tree -- keep it last
+    # and in one order, both k tables are unit-stride then)
+    con = [ix for ix in a_order if ix not in o_set]
+    con += [ix for ix in b_order if ix not in o_set and ix not in a_set]
+    ext = [size_dict[ix] for ix in con]
+    M = len(coords)
+    row_a, row_b = pick_request_rows(out_inds, coords, A, B)
+    order = np.lexsort((row_b, row_a))   # (stable: equal requests keep the caller's order)
+    zero = np.zeros(1, dtype=np.int64)
+
+    step = Step(kind=KIND_PAIR, kernel=KERNEL_PICK, a=A, b=B, c=C, node=node)
+    step.R, step.Bt, step.N, step.K, step.row_lo = M, 1, 1, prod(ext), 1
+    step.rows["A"] = (row_a[order], zero)
+    step.rows["B"] = (row_b[order], zero)
+    step.rows["C"] = (order.astype(np.int64), zero)
+    step.k_lo, (step.k_tabs["A"], step.k_tabs["B"]) = _rows_two_level(
+        ext, [[A.stride_of(ix) for ix in con], [B.stride_of(ix) for ix in con]])
+    step.n_tabs["B"] = step.n_tabs["C"] = zero
+    step.macs = M * step.K
+    # (what the step has to move: every distinct row of either operand once, the results)
+    step.elems_rw = (len(np.unique(row_a)) + len(np.unique(row_b))) * step.K + M
+    step.label = f"pick m{M} k{step.K}"
+    return step
+
+
+def build_pick_single(size_dict, src, out_inds, coords, C, node=-1):
+    """The same for a tree of one input: a SINGLE step with per-request rows (no new kernel)."""
+    src_unique = list(dict.fromkeys(src.inds))
+    o_set = set(out_inds)
+    if not o_set <= set(src_unique):
+        raise ValueError("Output index not present on the input term.")
+    if len(o_set) != len(out_inds):
+        raise ValueError("Repeated output indices are not supported.")
+    summed = [ix for ix in src_unique if ix not in o_set]
+    ext = [size_dict[ix] for ix in summed]
+    M = len(coords)
+    (row_a,) = pick_request_rows(out_inds, coords, src)
+    order = np.argsort(row_a, kind="stable")
+    zero = np.zeros(1, dtype=np.int64)
+    step = Step(kind=KIND_SINGLE, a=src, c=C, node=node)
+    step.R, step.row_lo = M, 1
+    step.rows["A"] = (row_a[order], zero)
+    step.rows["C"] = (order.astype(np.int64), zero)
+    step.K = prod(ext)
+    step.k_lo, (step.k_tabs["A"],) = _rows_two_level(ext, [[src.stride_of(ix) for ix in summed]])
+    step.elems_rw = M * step.K + M
+    step.label = f"pick single m{M} s{step.K}"
+    return step
+
+
+# --------------------------------------------------------------------------- #
 # whole-tree compilation
 # --------------------------------------------------------------------------- #
 
@@ -827,7 +928,7 @@ def choose_slice_group(tree, plan):
 
 
 def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min_elems=None, _pairs=None,
-                 stem_bf16x3=None, _group=None):
+                 stem_bf16x3=None, _group=None, pick=None, _pick_relayout=True):
     """Compile ``tree`` (possibly sliced) into a :class:`Plan` that computes
     ONE slice and accumulates it into the full result tensor.
 
@@ -840,7 +941,24 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
     consecutive stem steps are emitted as one STEM2 step (stem.py) -- the tree is
     compiled once without, the pairs are chosen on that plan's steps, and the
     tree is compiled again with them.
+
+    ``pick`` (``(M, len(tree.output))`` integers, one row per request, one column per output index): the plan
+    computes only those members of the output -- everything below the root as usual, the root as one sparse
+    step (``build_pick_step``) -- and its result is the ``(M,)`` vector of them in the caller's order.  The
+    root then belongs to no fused stem step and to no LDS-resident subtree; no output index may be sliced.
     """
+    if pick is not None:
+        out_sliced = [ix for ix in tree.output if ix in tree.sliced_inds]
+        if out_sliced:
+            raise ValueError(f"pick: the output indices {out_sliced} are sliced; slice inner indices only.")
+        pick = np.ascontiguousarray(pick, dtype=np.int64)
+        if pick.ndim != 2 or pick.shape[1] != len(tree.output):
+            raise ValueError(f"pick: coords of shape {pick.shape}, expected (M, {len(tree.output)}).")
+        if not 1 <= len(pick) <= PICK_MAX:
+            raise ValueError(f"pick: {len(pick)} requests; a plan takes 1 to {PICK_MAX}.")
+        for j, ix in enumerate(tree.output):
+            if pick[:, j].min() < 0 or pick[:, j].max() >= tree.size_dict[ix]:
+                raise ValueError(f"pick: a coordinate of output index {ix!r} is outside [0, {tree.size_dict[ix]}).")
     if fuse is None:
         fuse = os.environ.get("CTG_NO_FUSE", "0") in ("", "0")
     if _pairs is None and _group is None:
@@ -848,10 +966,11 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
         # choose the group indices on THAT plan's steps, compile once more with both
         pairs = {}
         plan = None
+        pick_kw = {} if pick is None else {"pick": pick, "_pick_relayout": _pick_relayout}
         if fuse and dtype == "complex64" and force_kernel is None and tree.N > 2:
             from .stem import find_pairs
 
-            plan = compile_tree(tree, dtype, order, force_kernel, fuse=False, _pairs={}, _group=())
+            plan = compile_tree(tree, dtype, order, force_kernel, fuse=False, _pairs={}, _group=(), **pick_kw)
             pairs = find_pairs(
                 plan, tree.size_dict,
                 min_elems=(
@@ -860,11 +979,15 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
                 ),
                 bf16x3=stem_bf16x3,   # (the pairs are priced in the arithmetic they will run in)
             )
+            if pick is not None:
+                # (the root is the sparse step: neither the last step of a fused tile nor a stem step of its own)
+                pairs = {k: v for k, v in pairs.items() if tree.root not in (k, v)}
         if plan is None or pairs:
-            plan = compile_tree(tree, dtype, order, force_kernel, fuse=False, _pairs=pairs, _group=())
+            plan = compile_tree(tree, dtype, order, force_kernel, fuse=False, _pairs=pairs, _group=(), **pick_kw)
         group = choose_slice_group(tree, plan)
         if group:
-            plan = compile_tree(tree, dtype, order, force_kernel, fuse=False, _pairs=pairs, _group=frozenset(group))
+            plan = compile_tree(tree, dtype, order, force_kernel, fuse=False, _pairs=pairs, _group=frozenset(group),
+                                **pick_kw)
         return plan
     pairs = _pairs or {}
     group = frozenset(_group or ())
@@ -898,6 +1021,10 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
     full_out_strides = dict(
         zip(tree.output, _row_major_strides(plan.result_shape))
     )
+    if pick is not None:
+        # (the result is the vector of the requested members)
+        plan.result_shape = (len(pick),)
+        plan.result_elems = len(pick)
 
     # -- slicing metadata
     sliced = list(tree.sliced_inds.values())
@@ -1039,7 +1166,8 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
                     return "group"
                 return "slice"
 
-            comps = ldsrun.choose_components(tree, dtype, plan.itemsize, node_class, pairs=pairs)
+            comps = ldsrun.choose_components(tree, dtype, plan.itemsize, node_class, pairs=pairs,
+                                             exclude=(tree.root,) if pick is not None else ())
         if comps:
             # (leaf preprocessing steps in the same class order as the pair steps below)
             leaf_order = sorted(range(N), key=lambda i: ldsrun.CLASS_RANK[node_class(i)])
@@ -1111,6 +1239,34 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
 
             return reorder
 
+    # A pick plan's root step reads, per request, one row of each child along the contracted indices: a child
+    # that is an arena intermediate keeps the indices the requests address first and the contracted ones last,
+    # in one order for both children -- both k tables of the root step are then unit-stride and every request
+    # offset is a multiple of K (16-byte loads).  Leaves keep the caller's layout.
+    if pick is not None and _pick_relayout and N > 1:
+        root_kids = tree.children[tree.root]
+        kept_root = set(root_order)
+        inner_order = consumer_order
+
+        def consumer_order(node):
+            if node not in root_kids:
+                return inner_order(node) if inner_order is not None else None
+
+            def reorder(natural):
+                return tuple(ix for ix in natural if ix in kept_root) + tuple(
+                    sorted((ix for ix in natural if ix not in kept_root), key=str)
+                )
+
+            return reorder
+
+    def pick_ref():
+        """The ``(M,)`` arena tensor the sparse root step writes."""
+        n = len(pick)
+        off = arena.alloc(n)
+        ref = TensorRef(SPACE_ARENA, off, -1, ("pick",), (1,), n)
+        arena_live[id(ref)] = (off, n)
+        return ref
+
     sequence = None
     if comps and level is not None:
         rank = ldsrun.CLASS_RANK
@@ -1122,7 +1278,11 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
     operand_node = {}   # id(TensorRef) -> the tree node whose tensor it is (LDS shadows)
     step_of_node = {}
 
-    if N == 1:
+    if N == 1 and pick is not None:
+        step = build_pick_single(size_dict, tensors[0], root_order, pick, pick_ref(), node=tree.root)
+        add(step)
+        final = step.c
+    elif N == 1:
         step = build_single_step(
             size_dict, tensors[0], root_order, arena_factory(), node=tree.root
         )
@@ -1250,7 +1410,9 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
                     else:
                         tr = first.c
                     steps_new = [first]
-            if steps_new is None or steps_new[0].kind == KIND_PAIR:
+            if is_root and pick is not None:
+                steps_new = (steps_new or []) + [build_pick_step(size_dict, tl, tr, p_inds, pick, pick_ref(), node=p)]
+            elif steps_new is None or steps_new[0].kind == KIND_PAIR:
                 steps_new = (steps_new or []) + [build_pair_step(
                     dtype,
                     size_dict,
@@ -1289,16 +1451,20 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
         plan.result_elems,
     )
     acc.c = res
-    rows_g = list(final.inds)
-    ext = [size_dict[ix] for ix in rows_g]
-    acc.R = prod(ext)
-    lo, tabs = _rows_two_level(
-        ext,
-        [
+    if pick is not None:
+        # (identity tables: request m of the step's vector onto request m of the result)
+        res.inds, res.strides = final.inds, (1,)
+        rows_g, ext = ["pick"], [len(pick)]
+        stride_lists = [[1], [1]]
+    else:
+        rows_g = list(final.inds)
+        ext = [size_dict[ix] for ix in rows_g]
+        stride_lists = [
             [final.stride_of(ix) for ix in rows_g],
             [res.stride_of(ix) for ix in rows_g],
-        ],
-    )
+        ]
+    acc.R = prod(ext)
+    lo, tabs = _rows_two_level(ext, stride_lists)
     acc.row_lo = lo
     acc.rows["A"], acc.rows["C"] = tabs
     acc.elems_rw = 0

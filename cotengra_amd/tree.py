@@ -1069,6 +1069,16 @@ class ContractionTree:
 
         return _tree_contractor(self, order).topk(*arrays, k=k, **kwargs)
 
+    def contract_pick(self, arrays, coords=None, indices=None, order=None, **kwargs):
+        """Only the requested members of :meth:`contract`'s result -- ``coords`` ``(M, len(output))`` or
+        ``indices`` ``(M,)`` flat positions in ``gathered_shape()``, as ``contract_sample`` / ``contract_topk``
+        return them -- through a sparse root step: the ``(M,)`` amplitudes in the caller's order, summed over
+        all slices; the full output never exists (``HipContractor.pick``; ``kwargs``: ``strip_exponent``,
+        ``check_zero``).  No output index may be sliced.  Not differentiable."""
+        from .contractor import _tree_contractor
+
+        return _tree_contractor(self, order).pick(*arrays, coords=coords, indices=indices, **kwargs)
+
     def contract_marginal(self, arrays, keep, order=None, **kwargs):
         """:meth:`contract` followed by the marginal of ``|result|^2`` over the output indices ``keep`` (a
         sequence of labels, or a list of such sequences) on the device (``HipContractor.marginal``; ``kwargs``:

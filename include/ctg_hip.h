@@ -89,7 +89,18 @@ enum {
  * launch (accum_group_kernel, workgroups dealt in proportion to the steps' rows; the
  * same bits as one launch per step); ctg_plan_create rejects a plan whose consecutive
  * accumulate steps write overlapping result ranges.  A plan with one accumulate step
- * launches accum_kernel as before. */
+ * launches accum_kernel as before.
+ *
+ * Added to ABI 10 WITHOUT a bump of CTG_ABI_VERSION (a new kernel code, no new symbol; plans without it are
+ * unchanged): kernel code 2 in word 1 of a pair record (kind 1) -- the sparse root step of a pick plan
+ * (cotengra_amd/plan.py: compile_tree(pick=...), csrc/ctg_pick.hip).  Such a record has
+ * N = 1, Bt = 1 and row_lo = 1: its R rows are requested members of the tree's output, the `hi` level of the
+ * three row tables holding, per request, its offset in A, in B and its position in the result of the step,
+ *   C[rowC(m)] = alpha * sum_k A[rowA(m) + kA(k)] * B[rowB(m) + kB(k)],
+ * and the plan's result is the vector of the requests (result_elems = R).  ctg_plan_create rejects code 2 on any
+ * other kind of record, with other extents, or with a row, k or n table absent (offset -1) (CTG_E_INVALID), and checks the per-request tables like every table
+ * (sum of the table maxima per operand inside its space).  The step launches alone, carries the slices of a
+ * batch like every thread-per-output step, and takes strip_exponent / check_zero like every pair step. */
 typedef struct ctg_plan_desc {
     int32_t dtype;                /* CTG_F32 .. CTG_C128 */
     int64_t n_inputs;
@@ -300,7 +311,9 @@ int ctg_exec_profile_slice(ctg_exec* exec, int64_t slice_id, float* ms);
  *   "pair_kred_kernel + pair_kred_finish_kernel<true|false>" lanes along a long k
  *   "pair_kred_multi_kernel<2|3|4> + pair_kred_finish_kernel<true|false>"
  * (two launches: the partial sums and the pass that adds them, a wavefront per
- * output when <true>).  Match by prefix. */
+ * output when <true>).  The sparse root step of a pick plan (kernel code 2) is
+ *   "pair_pick_kernel<float|double|c64|c128,VEC,SEG>"        VEC 1 | 2 adjacent k per load, SEG lanes per request
+ * or, few requests under a very long contraction, one of the two k-reduction names above.  Match by prefix. */
 int ctg_exec_step_kernel(ctg_exec* exec, int64_t step, char* buf, int64_t buflen);
 
 int ctg_exec_sync(ctg_exec* exec);
