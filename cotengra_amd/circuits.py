@@ -319,13 +319,20 @@ def top_chaotic(n, gates, marginal_qubits, bunches=1, top=1, seed=None, optimize
     return out
 
 
-def amplitudes_of(n, gates, bitstrings, optimize="greedy", dtype="complex64", target_size=None):
+def amplitudes_of(n, gates, bitstrings, optimize="greedy", dtype="complex64", target_size=None, chain=False):
     """Ideal amplitudes of given bitstrings -- measured or spoofed ones to be scored -- of the ``n``-qubit circuit
     ``gates``: the qubits on which all ``bitstrings`` agree are projected, the others left open, and of that one
     network's batch of ``2^k`` amplitudes only the requested members are contracted
     (``ContractionTree.contract_pick``: a sparse root step, the batch itself never exists).  One network, one
     tree (``optimize``: as for ``array_contract_tree``; ``target_size`` slices inner indices of the tree found),
     one call.
+
+    ``chain`` (``True``, or an ``int``: at most that many levels below the root): the requests are carried
+    down the tree -- a node below the root whose output legs the table addresses at few distinct projections
+    (``plan.pick_chain_nodes``: ``PICK_CHAIN_GAIN * M_c <= O_c``, its parent sparse too) is stored as ``M_c`` rows
+    of its other legs and computed by one row-sparse step, so cost and memory follow the
+    table, not ``2^k``.  Which nodes are sparse depends on the table through that rule: a request's bits are
+    therefore independent of the table's order and of duplicates, but not of which other requests are present.
 
     Returns a dict: ``bitstrings`` (as given), ``amplitudes`` (one per bitstring, in that order), ``p`` (their
     ``|amplitude|^2``, float64) and ``open_qubits`` (the qubits left open, ascending).
@@ -350,7 +357,7 @@ def amplitudes_of(n, gates, bitstrings, optimize="greedy", dtype="complex64", ta
         raise ValueError("optimize: the tree is not over this circuit's network.")
     if target_size is not None:
         tree = tree.slice(target_size=target_size, allow_outer=False)
-    amps = np.asarray(tree.contract_pick(arrays, coords=bits[:, open_qubits]))
+    amps = np.asarray(tree.contract_pick(arrays, coords=bits[:, open_qubits], chain=chain))
     return {"bitstrings": bitstrings, "amplitudes": amps, "p": np.abs(amps).astype(np.float64) ** 2,
             "open_qubits": open_qubits}
 

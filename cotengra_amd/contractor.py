@@ -351,10 +351,13 @@ class HipContractor:
         stem_bf16x3=None,
         crest_limit=None,
         pick=None,
+        pick_chain=False,
     ):
         # a request table (``pick_requests``): the contractor computes those members of the output only, its
         # result is the ``(M,)`` vector of them (``HipContractor.pick`` builds and caches such contractors)
         self._pick = pick
+        # ... with the requests carried down the tree as row-sparse intermediates (compile_tree(pick_chain=...))
+        self._pick_chain = pick_chain
         # the pick contractor this one built last (``_pick_contractor``): closed with it
         self._picker = None
         self._origin = tree  # whose ``contraction_cores`` hold this contractor's siblings
@@ -421,7 +424,7 @@ class HipContractor:
             plan = self._host_plans[dtype] = compile_tree(
                 self.tree, dtype, order=self.order, force_kernel=self.force_kernel,
                 fuse=self.fuse, fuse_min_elems=self.fuse_min_elems, stem_bf16x3=self.stem_bf16x3,
-                **({} if self._pick is None else {"pick": self._pick}),
+                **({} if self._pick is None else {"pick": self._pick, "pick_chain": self._pick_chain}),
             )
             return plan
 
@@ -838,9 +841,9 @@ class HipContractor:
 
     # ---- chosen members of the output: a sparse root step (csrc/ctg_pick.hip) -------------------- #
 
-    def _pick_contractor(self, req):
+    def _pick_contractor(self, req, chain=False):
         """The contractor of the request table ``req``, cached on the tree under ``("hip-pick", order, sha1 of
-        the int64 coords)``; it replaces -- and closes -- the pick contractor cached before it (its tables cost
+        the int64 coords, chain)``; it replaces -- and closes -- the pick contractor cached before it (its tables cost
         24 bytes per request and plan on the device, and there is no reason to keep many).  Under ``_PICK_LOCK``,
         which the caller keeps until the call on the returned contractor is over.  The contractor lives until
         another table replaces it or the contractor that built it is closed."""
@@ -848,7 +851,10 @@ class HipContractor:
 
         cores = self._origin.contraction_cores
         order = self.order if not callable(self.order) else id(self.order)
-        key = ("hip-pick", order, hashlib.sha1(np.ascontiguousarray(req, dtype=np.int64).tobytes()).hexdigest())
+        chain = chain if chain is True else int(chain)   # (False and 0 are one key: no chain)
+        # (True and 1 are equal as keys, and are different plans)
+        key = ("hip-pick", order, hashlib.sha1(np.ascontiguousarray(req, dtype=np.int64).tobytes()).hexdigest(),
+               "all" if chain is True else chain)
         fn = cores.get(key)
         if fn is not None and fn.tree is self.tree:
             return fn
@@ -858,12 +864,12 @@ class HipContractor:
         fn = cores[key] = HipContractor(
             self.tree, order=self.order, handle_slicing=True, device=self.device, force_kernel=self.force_kernel,
             fuse=self.fuse, fuse_min_elems=self.fuse_min_elems, stem_bf16x3=arith, crest_limit=self.crest_limit,
-            pick=req,
+            pick=req, pick_chain=chain,
         )
         self._picker = fn
         return fn
 
-    def pick(self, *arrays, coords=None, indices=None, strip_exponent=False, check_zero=False):
+    def pick(self, *arrays, coords=None, indices=None, strip_exponent=False, check_zero=False, chain=False):
         """Contract (all slices, as a call does) only the requested members of the output: ``coords``, ``(M,
         len(tree.output))`` integers, one column per output index in ``tree.output`` order, or ``indices``,
         ``(M,)`` flat row-major positions in ``tree.gathered_shape()`` -- the two forms ``SampleResult`` and
@@ -874,7 +880,14 @@ class HipContractor:
         exponent)`` as a call does.  ``M = 0``: an empty array, the device is not touched.  ``ValueError`` --
         before the device is touched -- for what :func:`pick_requests` refuses.  The result tensor of this
         contractor is not touched, but ``reuse=True`` of :meth:`topk` / :meth:`marginal` refuses to read it after
-        a pick.  Not differentiable."""
+        a pick.  Not differentiable.
+
+        ``chain`` (``True``, or an ``int``: at most that many levels below the root): the requests are carried
+        down the tree -- a node below the root whose output legs the table addresses at few distinct projections
+        (``plan.pick_chain_nodes``: ``PICK_CHAIN_GAIN * M_c <= O_c``, its parent sparse too) is stored as ``M_c`` rows
+        of its other legs and computed by one row-sparse step, so cost and memory follow the
+        table, not ``2^k``.  Which nodes are sparse depends on the table through that rule: a request's bits are
+        therefore independent of the table's order and of duplicates, but not of which other requests are present."""
         req = pick_requests(self.tree, coords, indices)
         with self._lock:
             self._reusable = None
@@ -889,7 +902,7 @@ class HipContractor:
                 out = np.zeros((0,), dtype=dtype)
             return (out, float("-inf")) if strip_exponent else out
         with _PICK_LOCK:
-            fn = self._pick_contractor(req)
+            fn = self._pick_contractor(req, chain)
             return fn._contract(arrays, False, check_zero, strip_exponent)
 
     # ---- top-k and marginals of the result on the device (csrc/ctg_reduce.hip) ------------------ #

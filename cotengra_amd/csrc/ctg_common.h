@@ -96,7 +96,11 @@ enum StemTab {
 // KERNEL_PICK (added to ABI 10 without a bump): the sparse root step of a pick plan -- a KIND_PAIR record with
 // N = 1, Bt = 1 and row_lo = 1 whose `hi` row tables hold one offset per requested member of the output
 // (cotengra_amd/plan.py: build_pick_step; kernel: ctg_pick.hip)
-enum Kernel { KERNEL_VALU = 0, KERNEL_MFMA = 1, KERNEL_PICK = 2 };
+// KERNEL_PICK_ROWS (likewise): the step of a row-sparse node below the root of a chained pick plan -- a KIND_PAIR
+// record with Bt = 1 in the thread-per-output addressing model whose `hi` row tables hold one offset per row of the
+// node (R = rows * row_lo), the `lo` level and the n tables running over the node's dense legs
+// (cotengra_amd/plan.py: build_pick_rows_step; kernel: ctg_pick_rows.hip)
+enum Kernel { KERNEL_VALU = 0, KERNEL_MFMA = 1, KERNEL_PICK = 2, KERNEL_PICK_ROWS = 3 };
 enum Space { SPACE_INPUTS = 0, SPACE_ARENA = 1, SPACE_RESULT = 2 };
 
 // Two-level row table: off(i) = hi[i / lo_size] + lo[i % lo_size].
@@ -542,6 +546,20 @@ hipError_t launch_pair_pick(int dtype, const StepArgs& p, int vec, void* scratch
                             hipStream_t stream);
 // "pair_pick_kernel<T,VEC,SEG>" (T: float, double, c64, c128), or what pair_valu_name says of the k-reduction route
 void pair_pick_name(int dtype, const StepArgs& p, int vec, int64_t scratch_bytes, char* buf, size_t n);
+// The form of pair_pick_rows_kernel that runs a KERNEL_PICK_ROWS step, the one place that decides it (its mirror
+// for the planner's tests: cotengra_amd/plan.py: pick_rows_route): the matrix-core form (complex64, dtype code 2)
+// gives a wave one row and 32 of its row_lo dense positions on A against up to 32 columns, so it wants a whole
+// tile of positions and enough columns and contraction to feed v_mfma_f32_32x32x2_f32; everything else takes the
+// vector form.  A function of (row_lo, K, N, dtype) alone.  (A step whose B operand moves with the position --
+// a batch leg, rowB.lo not all zero: `b_fixed` = 0, found once per step on the host -- has no matrix form.)
+constexpr int64_t kPickRowsMfmaMinRowLo = 32, kPickRowsMfmaMinN = 8, kPickRowsMfmaMinK = 8;
+inline bool pick_rows_route_mfma(int64_t row_lo, int64_t K, int64_t N, int dtype) {
+    return dtype == 2 && row_lo >= kPickRowsMfmaMinRowLo && N >= kPickRowsMfmaMinN && K >= kPickRowsMfmaMinK;
+}
+// vec: as for launch_pair_pick; b_fixed: 1 = rowB.lo is all zero
+hipError_t launch_pair_pick_rows(int dtype, const StepArgs& p, int vec, int b_fixed, hipStream_t stream);
+// "pair_pick_rows_kernel<T,VEC>" (T: float, double, c64, c128) or "pair_pick_rows_mfma_kernel<c64>"
+void pair_pick_rows_name(int dtype, const StepArgs& p, int vec, int b_fixed, char* buf, size_t n);
 // Independent small steps of the tiled fast kernel sharing one launch (same tile
 // shape and gather width: `key`); item i owns workgroups [block_begin, +n_blocks).
 struct FastGroupItem {

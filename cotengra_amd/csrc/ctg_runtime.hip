@@ -240,8 +240,15 @@ int validate_plan(ctg_plan* p) {
             if (rc != CTG_OK) return rc;
             continue;
         }
-        if (r[W_KERNEL] < 0 || r[W_KERNEL] > 2)
+        if (r[W_KERNEL] < 0 || r[W_KERNEL] > 3)
             return fail(CTG_E_INVALID, "step %lld: bad kernel", (long long)s);
+        if (r[W_KERNEL] == KERNEL_PICK_ROWS && (kind != KIND_PAIR || r[W_BT] != 1))
+            return fail(CTG_E_INVALID, "step %lld: the pick rows kernel executes pair steps with Bt = 1 only", (long long)s);
+        if (r[W_KERNEL] == KERNEL_PICK_ROWS)   // (pick_vec_ok and the kernel read every table: none may be absent)
+            for (int w : {W_ROWA_HI, W_ROWA_LO, W_ROWB_HI, W_ROWB_LO, W_ROWC_HI, W_ROWC_LO, W_KA_HI, W_KA, W_KB_HI,
+                          W_KB, W_NB, W_NC})
+                if (r[w] < 0)
+                    return fail(CTG_E_INVALID, "step %lld: the pick rows kernel needs every row, k and n table", (long long)s);
         if (r[W_KERNEL] == KERNEL_PICK && (kind != KIND_PAIR || r[W_N] != 1 || r[W_BT] != 1 || r[W_ROW_LO] != 1))
             return fail(CTG_E_INVALID, "step %lld: the pick kernel executes pair steps with N = 1, Bt = 1 and row_lo = 1 only",
                         (long long)s);
@@ -600,8 +607,9 @@ bool all_even(const ctg_plan* p, int64_t w, int64_t len, int64_t stride = 1) {
     return true;
 }
 
-// A KERNEL_PICK step can read two adjacent k per load (pair_pick_kernel<T, 2, SEG>): the fast level of both k
-// tables is unit-stride and of even length, and every other offset of either operand is even.
+// A KERNEL_PICK / KERNEL_PICK_ROWS step can read two adjacent k per load (pair_pick_kernel<T, 2, SEG>,
+// pair_pick_rows_kernel<T, 2>): the fast level of both k tables is unit-stride and of even length, and every other
+// offset of either operand is even.
 bool pick_vec_ok(const ctg_plan* p, const int64_t* r) {
     const int64_t k_lo = r[W_K_LO];
     if ((k_lo & 1) || (r[W_A_OFF] & 1) || (r[W_B_OFF] & 1)) return false;
@@ -609,7 +617,9 @@ bool pick_vec_ok(const ctg_plan* p, const int64_t* r) {
         if (p->tables[r[W_KA] + i] != i || p->tables[r[W_KB] + i] != i) return false;
     if (!all_even(p, r[W_KA_HI], r[W_K_HI_LEN]) || !all_even(p, r[W_KB_HI], r[W_K_HI_LEN])) return false;
     if (!all_even(p, r[W_ROWA_HI], r[W_ROW_HI_LEN]) || !all_even(p, r[W_ROWB_HI], r[W_ROW_HI_LEN])) return false;
-    if (!all_even(p, r[W_ROWA_LO], 1) || !all_even(p, r[W_ROWB_LO], 1) || !all_even(p, r[W_NB], 1)) return false;
+    // (a KERNEL_PICK record has row_lo = N = 1)
+    if (!all_even(p, r[W_ROWA_LO], r[W_ROW_LO]) || !all_even(p, r[W_ROWB_LO], r[W_ROW_LO]) || !all_even(p, r[W_NB], r[W_N]))
+        return false;
     if (p->arena_elems & 1) return false;   // (the replicas of a slice batch)
     for (int lw : {W_A_LEAF, W_B_LEAF})
         if (r[lw] >= 0)
@@ -848,6 +858,13 @@ int build_hints_into(ctg_exec* e, std::vector<MfmaHints>& hints, int64_t zmult,
     for (int64_t s = 0; s < p->n_steps; ++s) {
         const int64_t* r = &p->steps[s * STEP_WORDS];
         if (r[W_KIND] == KIND_PAIR && r[W_KERNEL] == KERNEL_PICK) hints[s].vecA = pick_vec_ok(p, r) ? 1 : 0;
+        if (r[W_KIND] == KIND_PAIR && r[W_KERNEL] == KERNEL_PICK_ROWS) {
+            hints[s].vecA = pick_vec_ok(p, r) ? 1 : 0;
+            // (`fast` of a pick rows step: B does not move with the position inside a row -- the matrix-core form's condition)
+            bool fixed = true;
+            for (int64_t i = 0; i < r[W_ROW_LO] && fixed; ++i) fixed = p->tables[r[W_ROWB_LO] + i] == 0;
+            hints[s].fast = fixed ? 1 : 0;
+        }
         if (r[W_KIND] != KIND_PAIR || r[W_KERNEL] != KERNEL_MFMA) continue;
         MfmaHints& h = hints[s];
         if (p->dtype != CTG_C64) {
@@ -1021,6 +1038,7 @@ bool step_needs_scratch(const ctg_exec* e, int64_t s) {
     const int64_t* r = &p->steps[s * STEP_WORDS];
     if (r[W_KIND] != KIND_PAIR) return false;
     if (r[W_KERNEL] == KERNEL_PICK) return pick_route_kred(r[W_R], r[W_K]);
+    if (r[W_KERNEL] == KERNEL_PICK_ROWS) return false;
     if (r[W_KERNEL] != KERNEL_MFMA) return !valu_thread_per_output(e->args[s]);
     if (p->dtype != CTG_C64) return false;   // (the real / double kernels have no k-split)
     auto needs = [](const MfmaHints& h) {
@@ -1340,6 +1358,8 @@ int launch_step(ctg_exec* e, int64_t s, hipStream_t stream) {
                 }
             } else if (r[W_KERNEL] == KERNEL_PICK)
                 err = launch_pair_pick(p->dtype, e->args[s], e->hints[s].vecA, e->d_scratch, kScratchBytes, stream);
+            else if (r[W_KERNEL] == KERNEL_PICK_ROWS)
+                err = launch_pair_pick_rows(p->dtype, e->args[s], e->hints[s].vecA, e->hints[s].fast, stream);
             else
                 err = launch_pair_valu(p->dtype, e->args[s], e->d_scratch, kScratchBytes, stream);
             break;
@@ -1389,7 +1409,7 @@ int build_groups(ctg_exec* e) {
     auto class_of = [&](int64_t s) -> int {
         const int64_t* r = &p->steps[s * STEP_WORDS];
         if (off || r[W_KIND] != KIND_PAIR || e->invariant[s] || lds_member(s)) return -1;
-        if (r[W_KERNEL] == KERNEL_PICK) return -1;   // (its own kernel: never inside a shared launch)
+        if (r[W_KERNEL] == KERNEL_PICK || r[W_KERNEL] == KERNEL_PICK_ROWS) return -1;   // (their own kernels: never inside a shared launch)
         if (r[W_KERNEL] != KERNEL_MFMA) {
             if (!valu_thread_per_output(e->args[s])) return -1;
             ValuGroupItem it;
@@ -2694,6 +2714,8 @@ int ctg_exec_step_kernel(ctg_exec* e, int64_t step, char* buf, int64_t buflen) {
         pair_mfma_c64_name(e->args[step], h, kScratchBytes, name, sizeof(name));
     } else if (r[W_KERNEL] == KERNEL_PICK) {
         pair_pick_name(p->dtype, e->args[step], e->hints[step].vecA, kScratchBytes, name, sizeof(name));
+    } else if (r[W_KERNEL] == KERNEL_PICK_ROWS) {
+        pair_pick_rows_name(p->dtype, e->args[step], e->hints[step].vecA, e->hints[step].fast, name, sizeof(name));
     } else {
         pair_valu_name(p->dtype, e->args[step], kScratchBytes, name, sizeof(name));
     }

@@ -218,13 +218,20 @@ class ContractExpression:
         self._after_reduce()
         return out
 
-    def pick(self, *arrays, coords=None, indices=None, **kwargs):
+    def pick(self, *arrays, coords=None, indices=None, chain=False, **kwargs):
         """Only the requested members of ``expr(*arrays)`` -- ``coords`` ``(M, len(output))`` or ``indices``
         ``(M,)`` flat positions -- through a sparse root step (``HipContractor.pick``); the expression's own
-        ``strip_exponent`` / ``check_zero`` unless given."""
+        ``strip_exponent`` / ``check_zero`` unless given.
+
+        ``chain`` (``True``, or an ``int``: at most that many levels below the root): the requests are carried
+        down the tree -- a node below the root whose output legs the table addresses at few distinct projections
+        (``plan.pick_chain_nodes``: ``PICK_CHAIN_GAIN * M_c <= O_c``, its parent sparse too) is stored as ``M_c`` rows
+        of its other legs and computed by one row-sparse step, so cost and memory follow the
+        table, not ``2^k``.  Which nodes are sparse depends on the table through that rule: a request's bits are
+        therefore independent of the table's order and of duplicates, but not of which other requests are present."""
         kwargs.setdefault("strip_exponent", self.fn.strip_exponent)
         kwargs.setdefault("check_zero", self.fn.check_zero)
-        return self.fn.pick(*arrays, coords=coords, indices=indices, **kwargs)
+        return self.fn.pick(*arrays, coords=coords, indices=indices, chain=chain, **kwargs)
 
     def marginal(self, *arrays, keep, **kwargs):
         """``expr(*arrays)`` followed by the marginal of ``|result|^2`` over the output indices ``keep`` on the

@@ -64,7 +64,12 @@ KIND_STEM2 = 3  # two consecutive pair steps of a stem as one launch (stem.py)
 KERNEL_VALU = 0  # one thread per output element, any dtype / any shape
 KERNEL_MFMA = 1  # matrix-core kernels (complex64 on fp32 MFMA, complex128 on fp64 MFMA)
 KERNEL_PICK = 2  # sparse root step: one row per requested member of the output (build_pick_step, csrc/ctg_pick.hip)
+KERNEL_PICK_ROWS = 3  # sparse step below the root: a row-sparse node of a chained pick plan (build_pick_rows_step, csrc/ctg_pick_rows.hip)
 PICK_MAX = 1 << 24  # requests of one pick plan (its three row tables cost 24 bytes each on the device)
+# A child of a sparse node is stored row-sparse when its distinct request projections number at most 1 / GAIN of
+# its dense positions (pick_chain_nodes).  A guess: measured on two kinds of tree only, to be
+# revisited whenever tools/pick_chain_timing.py is run again.
+PICK_CHAIN_GAIN = 2
 
 SPACE_INPUTS = 0
 SPACE_ARENA = 1
@@ -501,7 +506,7 @@ class Plan:
                 {
                     "step": i,
                     "kind": ("single", "pair", "accum", "stem2")[s.kind],
-                    "kernel": ("valu", "mfma", "pick")[s.kernel],
+                    "kernel": ("valu", "mfma", "pick", "pick_rows")[s.kernel],
                     "R": s.R,
                     "Bt": s.Bt,
                     "K": s.K,
@@ -783,14 +788,16 @@ def pick_request_rows(out_inds, coords, *operands):
     return rows
 
 
-def build_pick_step(size_dict, l, r, out_inds, coords, C, node=-1):
+def build_pick_step(size_dict, l, r, out_inds, coords, C, node=-1, sparse_rows=None):
     """Lower the root einsum ``l, r -> out_inds`` at the requests ``coords`` (``(M, len(out_inds))`` int64) to
-    one PAIR step of kernel ``KERNEL_PICK``; ``C`` is the ``(M,)`` tensor that receives them."""
+    one PAIR step of kernel ``KERNEL_PICK``; ``C`` is the ``(M,)`` tensor that receives them.  ``sparse_rows``
+    (chained plans): ``id(child tensor) -> per-request offset`` for a child that is stored row-sparse."""
     o_set = set(out_inds)
-    if not o_set <= (set(l.inds) | set(r.inds)):
+    sparse_rows = sparse_rows or {}
+    if not sparse_rows and not o_set <= (set(l.inds) | set(r.inds)):
         raise ValueError(f"Output indices {o_set - (set(l.inds) | set(r.inds))} not found on any input.")
     A, B = pick_rows_operand(size_dict, l, r, out_inds)
-    a_order, b_order = list(dict.fromkeys(A.inds)), list(dict.fromkeys(B.inds))
+    a_order, b_order = ([ix for ix in dict.fromkeys(t.inds) if not is_rows_axis(ix)] for t in (A, B))
     a_set = set(a_order)
     # (the contracted group in A's memory order: children laid out for this step -- compile_tree -- keep it last
     # and in one order, both k tables are unit-stride then)
@@ -798,7 +805,8 @@ def build_pick_step(size_dict, l, r, out_inds, coords, C, node=-1):
     con += [ix for ix in b_order if ix not in o_set and ix not in a_set]
     ext = [size_dict[ix] for ix in con]
     M = len(coords)
-    row_a, row_b = pick_request_rows(out_inds, coords, A, B)
+    row_a, row_b = (sparse_rows[id(t)] if id(t) in sparse_rows else pick_request_rows(out_inds, coords, t)[0]
+                    for t in (A, B))
     order = np.lexsort((row_b, row_a))   # (stable: equal requests keep the caller's order)
     zero = np.zeros(1, dtype=np.int64)
 
@@ -839,6 +847,163 @@ def build_pick_single(size_dict, src, out_inds, coords, C, node=-1):
     step.k_lo, (step.k_tabs["A"],) = _rows_two_level(ext, [[src.stride_of(ix) for ix in summed]])
     step.elems_rw = M * step.K + M
     step.label = f"pick single m{M} s{step.K}"
+    return step
+
+
+# --------------------------------------------------------------------------- #
+# sparse steps below the root: row-sparse intermediates (compile_tree(pick=..., pick_chain=...))
+# --------------------------------------------------------------------------- #
+#
+# The requests address a node's tensor only through the output indices it carries.  A node with M_c distinct
+# projections of the request table onto those legs, against O_c positions of them, is stored as M_c rows of its
+# other ("dense") legs -- (M_c, dense legs...) row-major, row j the j-th distinct projection in lexicographic
+# order of the coordinates taken in tree.output order -- and computed by one thread-per-output pair step that
+# reads, per row, one sub-tensor of each child:
+#
+#     C[rowC.hi[m] + rowC.lo[i] + nC[n]] = alpha * sum_k A[rowA.hi[m] + rowA.lo[i] + kA(k)]
+#                                                        * B[rowB.hi[m] + rowB.lo[i] + kB(k) + nB[n]]
+#     m < M_c, i < row_lo, n < N, R = M_c * row_lo
+#
+# rowX.hi[m]: the row's coordinates times the strides of a dense child or a leaf; (the position of the row's
+# projection among a sparse child's rows) * D_child.  rowC.hi[m] = j(m) * D_c.
+
+
+def rows_axis(node):
+    """The label of the leading (row) axis of a sparse node's tensor: no index of any tree."""
+    return ("pick rows", node)
+
+
+def is_rows_axis(ix):
+    return isinstance(ix, tuple) and len(ix) == 2 and ix[0] == "pick rows"
+
+
+def pick_projection(tree, coords, node):
+    """``(cols, uniq, inverse)`` of the request table restricted to the output legs of ``node``: the columns
+    of ``coords`` (positions in ``tree.output``), the distinct rows in lexicographic order, and per request
+    the position of its projection among them."""
+    legs = tree.get_legs(node)
+    cols = [j for j, ix in enumerate(tree.output) if ix in legs]
+    if not cols:
+        return cols, np.zeros((1, 0), dtype=np.int64), np.zeros(len(coords), dtype=np.int64)
+    sizes = [tree.size_dict[tree.output[j]] for j in cols]
+    if prod(sizes) < (1 << 62):
+        # (one row-major key per request: its order is the lexicographic order of the coordinates)
+        keys, inverse = np.unique(np.ravel_multi_index(tuple(coords[:, j] for j in cols), sizes), return_inverse=True)
+        uniq = np.stack(np.unravel_index(keys, sizes), axis=1).astype(np.int64)
+    else:
+        uniq, inverse = np.unique(coords[:, cols], axis=0, return_inverse=True)
+    return cols, uniq, np.asarray(inverse, dtype=np.int64).reshape(-1)
+
+
+def pick_chain_nodes(tree, coords, chain=True):
+    """The sparse nodes below the root of a chained pick plan, top down: ``[(node, M_c, O_c, D_c)]`` with
+    ``M_c`` the distinct rows of ``coords`` restricted to the output legs of the node, ``O_c`` the product of
+    those legs' sizes and ``D_c`` the product of its other (dense) legs.
+
+    The root is sparse.  A child of a sparse node is sparse if it is not a leaf, carries at least one output
+    leg and ``PICK_CHAIN_GAIN * M_c <= O_c``; a node whose parent is not sparse never is.  ``chain``: ``True``,
+    or the number of levels below the root at most (``False`` / 0: none)."""
+    return [t[:4] for t in _pick_chain_walk(tree, coords, chain)]
+
+
+def _pick_chain_walk(tree, coords, chain):
+    """``pick_chain_nodes`` with, per node, the position of every request's projection among its rows."""
+    if chain is None or chain is False:
+        return []
+    limit = None if chain is True else int(chain)
+    coords = np.ascontiguousarray(coords, dtype=np.int64)
+    out_set = set(tree.output)
+    found, frontier = [], [(tree.root, 0)]
+    while frontier:
+        node, depth = frontier.pop(0)
+        if (limit is not None and depth >= limit) or tree.N == 1:
+            continue
+        for c in tree.children[node]:
+            if tree.is_leaf(c):
+                continue
+            legs = tree.get_legs(c)
+            out_legs = [ix for ix in legs if ix in out_set]
+            if not out_legs:
+                continue
+            _, uniq, inverse = pick_projection(tree, coords, c)
+            M_c = len(uniq)
+            O_c = prod(tree.size_dict[ix] for ix in out_legs)
+            if PICK_CHAIN_GAIN * M_c > O_c:
+                continue
+            D_c = prod(tree.size_dict[ix] for ix in legs if ix not in out_set)
+            found.append((c, M_c, O_c, D_c, inverse))
+            frontier.append((c, depth + 1))
+    return found
+
+
+# The route of a sparse step below the root, mirrored from the launcher for the planner's tests
+# (csrc/ctg_common.h: pick_rows_route, kPickRowsMfma*): the matrix-core form takes complex64 steps whose rows have
+# at least a 32-row tile of dense positions on A and enough columns and contraction to feed it.
+PICK_ROWS_MFMA_MIN_ROW_LO = 32
+PICK_ROWS_MFMA_MIN_N = 8
+PICK_ROWS_MFMA_MIN_K = 8
+
+
+def pick_rows_route(row_lo, K, N, dtype):
+    """``"mfma"`` or ``"vector"``: the form of ``pair_pick_rows_kernel`` that runs a sparse step below the root
+    -- a function of ``(row_lo, K, N, dtype)`` alone (a step whose B operand carries a batch leg, ``rowB.lo``
+    not all zero, always takes the vector form)."""
+    if (dtype == "complex64" and row_lo >= PICK_ROWS_MFMA_MIN_ROW_LO and N >= PICK_ROWS_MFMA_MIN_N
+            and K >= PICK_ROWS_MFMA_MIN_K):
+        return "mfma"
+    return "vector"
+
+
+def build_pick_rows_step(size_dict, l, r, dense_out, addressed, n_rows, row_l, row_r, out_ref_factory, node=-1):
+    """Lower the step of a sparse node below the root to one PAIR step of kernel ``KERNEL_PICK_ROWS``.
+
+    ``l`` / ``r``: the children's tensors (a sparse child carries its rows axis, ``rows_axis``, in front);
+    ``dense_out``: the dense legs of the result; ``addressed``: the tree's output indices (what the rows stand
+    for); ``row_l`` / ``row_r``: per canonical row of the result (``n_rows`` of them) the offset of that row's
+    sub-tensor in each child.  ``out_ref_factory(inds, natural)`` allocates the ``(n_rows, dense legs...)``
+    result, ``natural`` being the order of the dense legs the step prefers."""
+    d_set = set(dense_out)
+    dense_of = lambda t: [ix for ix in dict.fromkeys(t.inds) if not is_rows_axis(ix) and ix not in addressed]  # noqa: E731
+    l_inds, r_inds = dense_of(l), dense_of(r)
+    if not d_set <= (set(l_inds) | set(r_inds)):
+        raise ValueError(f"Output indices {d_set - (set(l_inds) | set(r_inds))} not found on any input.")
+    # (the rule of pick_rows_operand on the dense legs: more kept elements supply the rows, ties the left one)
+    rows_l = prod(size_dict[ix] for ix in l_inds if ix in d_set and ix not in r_inds)
+    rows_r = prod(size_dict[ix] for ix in r_inds if ix in d_set and ix not in l_inds)
+    if rows_r > rows_l:
+        A, B, a_order, b_order, row_a, row_b = r, l, r_inds, l_inds, row_r, row_l
+    else:
+        A, B, a_order, b_order, row_a, row_b = l, r, l_inds, r_inds, row_l, row_r
+    a_set, b_set = set(a_order), set(b_order)
+    # i: the dense legs of the result that A carries (one kept dense on both -- a hyper leg -- counts on both,
+    # as a batch leg of build_pair_step's thread-per-output branch); n: those only B carries
+    rows_g = [ix for ix in a_order if ix in d_set]
+    keep_b = [ix for ix in b_order if ix in d_set and ix not in a_set]
+    con = [ix for ix in a_order if ix not in d_set]
+    con += [ix for ix in b_order if ix not in d_set and ix not in a_set]
+    ext = lambda g: [size_dict[ix] for ix in g]  # noqa: E731
+    row_lo, K, N = prod(ext(rows_g)), prod(ext(con)), prod(ext(keep_b))
+
+    C = out_ref_factory(tuple(dense_out), tuple(rows_g) + tuple(keep_b))
+    D_c = prod(ext(dense_out))
+    row_a, row_b = np.asarray(row_a, dtype=np.int64), np.asarray(row_b, dtype=np.int64)
+    order = np.lexsort((row_b, row_a))   # (consecutive rows share A; rowC carries the canonical position)
+
+    step = Step(kind=KIND_PAIR, kernel=KERNEL_PICK_ROWS, a=A, b=B, c=C, node=node)
+    step.R, step.Bt, step.N, step.K, step.row_lo = n_rows * row_lo, 1, N, K, row_lo
+    step.rows["A"] = (row_a[order], group_table(ext(rows_g), [A.stride_of(ix) for ix in rows_g]))
+    step.rows["B"] = (row_b[order], group_table(ext(rows_g), [B.stride_of(ix) for ix in rows_g]))
+    step.rows["C"] = (order.astype(np.int64) * D_c, group_table(ext(rows_g), [C.stride_of(ix) for ix in rows_g]))
+    step.k_lo, (step.k_tabs["A"], step.k_tabs["B"]) = _rows_two_level(
+        ext(con), [[A.stride_of(ix) for ix in con], [B.stride_of(ix) for ix in con]])
+    step.n_tabs["B"] = group_table(ext(keep_b), [B.stride_of(ix) for ix in keep_b])
+    step.n_tabs["C"] = group_table(ext(keep_b), [C.stride_of(ix) for ix in keep_b])
+    step.macs = n_rows * row_lo * K * N
+    # (what the step has to move: every distinct sub-tensor of either operand once, the result)
+    a_sub = prod(ext(a_order))
+    b_sub = prod(ext(b_order))
+    step.elems_rw = len(np.unique(row_a)) * a_sub + len(np.unique(row_b)) * b_sub + n_rows * D_c
+    step.label = f"pick rows m{n_rows} i{row_lo} k{K} n{N}"
     return step
 
 
@@ -928,7 +1093,7 @@ def choose_slice_group(tree, plan):
 
 
 def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min_elems=None, _pairs=None,
-                 stem_bf16x3=None, _group=None, pick=None, _pick_relayout=True):
+                 stem_bf16x3=None, _group=None, pick=None, _pick_relayout=True, pick_chain=False, _pick_sparse=None):
     """Compile ``tree`` (possibly sliced) into a :class:`Plan` that computes
     ONE slice and accumulates it into the full result tensor.
 
@@ -946,6 +1111,11 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
     computes only those members of the output -- everything below the root as usual, the root as one sparse
     step (``build_pick_step``) -- and its result is the ``(M,)`` vector of them in the caller's order.  The
     root then belongs to no fused stem step and to no LDS-resident subtree; no output index may be sliced.
+
+    ``pick_chain`` (``True``, or an ``int``: at most that many levels below the root; needs ``pick``): nodes
+    below the root that few distinct request projections address (``pick_chain_nodes``) are stored row-sparse
+    and computed by one ``KERNEL_PICK_ROWS`` step each (``build_pick_rows_step``); like the root they belong to
+    no fused stem step and to no LDS-resident subtree.  ``False``: the plan of ``pick`` alone, record for record.
     """
     if pick is not None:
         out_sliced = [ix for ix in tree.output if ix in tree.sliced_inds]
@@ -959,6 +1129,8 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
         for j, ix in enumerate(tree.output):
             if pick[:, j].min() < 0 or pick[:, j].max() >= tree.size_dict[ix]:
                 raise ValueError(f"pick: a coordinate of output index {ix!r} is outside [0, {tree.size_dict[ix]}).")
+    if pick is None and pick_chain:
+        raise ValueError("pick_chain: there is no request table (pick) to chain.")
     if fuse is None:
         fuse = os.environ.get("CTG_NO_FUSE", "0") in ("", "0")
     if _pairs is None and _group is None:
@@ -966,7 +1138,12 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
         # choose the group indices on THAT plan's steps, compile once more with both
         pairs = {}
         plan = None
-        pick_kw = {} if pick is None else {"pick": pick, "_pick_relayout": _pick_relayout}
+        pick_kw = {}
+        if pick is not None:
+            # (the sparse set is a function of the tree and the table: found once for the passes below)
+            walk = _pick_chain_walk(tree, pick, pick_chain)
+            pick_kw = {"pick": pick, "_pick_relayout": _pick_relayout, "pick_chain": pick_chain, "_pick_sparse": walk}
+            sparse_top = {tree.root} | {t[0] for t in walk}
         if fuse and dtype == "complex64" and force_kernel is None and tree.N > 2:
             from .stem import find_pairs
 
@@ -980,8 +1157,9 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
                 bf16x3=stem_bf16x3,   # (the pairs are priced in the arithmetic they will run in)
             )
             if pick is not None:
-                # (the root is the sparse step: neither the last step of a fused tile nor a stem step of its own)
-                pairs = {k: v for k, v in pairs.items() if tree.root not in (k, v)}
+                # (the root is the sparse step: neither the last step of a fused tile nor a stem step of its own;
+                # the sparse nodes below it -- pick_chain -- likewise)
+                pairs = {k: v for k, v in pairs.items() if k not in sparse_top and v not in sparse_top}
         if plan is None or pairs:
             plan = compile_tree(tree, dtype, order, force_kernel, fuse=False, _pairs=pairs, _group=(), **pick_kw)
         group = choose_slice_group(tree, plan)
@@ -991,6 +1169,13 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
         return plan
     pairs = _pairs or {}
     group = frozenset(_group or ())
+    # row-sparse nodes below the root (pick_chain): node -> (M_c, per-request row, a request of each row)
+    sparse = {}
+    if pick is not None and pick_chain:
+        for c, M_c, _, _, inverse in (_pick_sparse if _pick_sparse is not None else _pick_chain_walk(tree, pick, pick_chain)):
+            rep_ = np.zeros(M_c, dtype=np.int64)
+            rep_[inverse[::-1]] = np.arange(len(pick), dtype=np.int64)[::-1]   # (the first request of each row)
+            sparse[c] = (M_c, inverse, rep_)
     pair_second = {v: k for k, v in pairs.items() if v != k}   # (k: k = a single step on the stem kernel)
     stem_pending = {}  # first node of a pair -> (A, B1, legs of the intermediate)
     plan = Plan(dtype)
@@ -1062,12 +1247,15 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
     persistent_refs = []
     parena = Arena()
 
-    def arena_factory(force_order=None, invariant=False, reorder=None):
+    def arena_factory(force_order=None, invariant=False, reorder=None, rows=None):
+        # (``rows``: (M_c, label) of a row-sparse node -- its tensor is (M_c, dense legs...) row-major)
         def make(inds, natural):
             order_ = force_order if force_order is not None else natural
             if force_order is None and reorder is not None:
                 order_ = reorder(natural)
             shape = [size_dict[ix] for ix in order_]
+            if rows is not None:
+                shape, order_ = [rows[0]] + shape, (rows[1],) + tuple(order_)
             n = prod(shape)
             # invariant outputs live in their own region placed behind the
             # per-slice arena (relocated below once its peak is known): they
@@ -1167,7 +1355,7 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
                 return "slice"
 
             comps = ldsrun.choose_components(tree, dtype, plan.itemsize, node_class, pairs=pairs,
-                                             exclude=(tree.root,) if pick is not None else ())
+                                             exclude=(tree.root, *sparse) if pick is not None else ())
         if comps:
             # (leaf preprocessing steps in the same class order as the pair steps below)
             leaf_order = sorted(range(N), key=lambda i: ldsrun.CLASS_RANK[node_class(i)])
@@ -1243,18 +1431,26 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
     # that is an arena intermediate keeps the indices the requests address first and the contracted ones last,
     # in one order for both children -- both k tables of the root step are then unit-stride and every request
     # offset is a multiple of K (16-byte loads).  Leaves keep the caller's layout.
+    # The same one level down for the children of every sparse node below the root (pick_chain): the output legs
+    # the rows address first, the dense legs the parent keeps next, the contracted ones last; a sparse child's
+    # tensor holds dense legs only.
     if pick is not None and _pick_relayout and N > 1:
-        root_kids = tree.children[tree.root]
-        kept_root = set(root_order)
+        out_set = set(root_order)
+        kept_of = {}   # child of a sparse node -> the legs that node keeps
+        for u in (tree.root, *sparse):
+            for c in tree.children[u]:
+                kept_of[c] = out_set if u == tree.root else set(tree.get_legs(u))
         inner_order = consumer_order
 
         def consumer_order(node):
-            if node not in root_kids:
+            if node not in kept_of:
                 return inner_order(node) if inner_order is not None else None
+            kept_up = kept_of[node]
 
             def reorder(natural):
-                return tuple(ix for ix in natural if ix in kept_root) + tuple(
-                    sorted((ix for ix in natural if ix not in kept_root), key=str)
+                return tuple(ix for ix in natural if ix in kept_up and ix in out_set) + tuple(
+                    ix for ix in natural if ix in kept_up and ix not in out_set) + tuple(
+                    sorted((ix for ix in natural if ix not in kept_up), key=str)
                 )
 
             return reorder
@@ -1306,6 +1502,7 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
                 root_order if is_root else None,
                 invariant=inv or kept_for_group(p),
                 reorder=consumer_order(p) if consumer_order is not None else None,
+                rows=(sparse[p][0], rows_axis(p)) if p in sparse else None,
             )
             p_inds = root_order if is_root else tuple(tree.get_legs(p))
             tl, tr = tensors.pop(l), tensors.pop(r)
@@ -1411,7 +1608,19 @@ def compile_tree(tree, dtype, order=None, force_kernel=None, fuse=None, fuse_min
                         tr = first.c
                     steps_new = [first]
             if is_root and pick is not None:
-                steps_new = (steps_new or []) + [build_pick_step(size_dict, tl, tr, p_inds, pick, pick_ref(), node=p)]
+                # (a sparse child: the request's row in it, pick_chain)
+                at = {id(t): sparse[c][1] * (t.size // sparse[c][0]) for c, t in ((l, tl), (r, tr)) if c in sparse}
+                steps_new = (steps_new or []) + [build_pick_step(size_dict, tl, tr, p_inds, pick, pick_ref(), node=p,
+                                                                 sparse_rows=at)]
+            elif p in sparse:
+                # a row of p reads the sub-tensor of each child that its first request addresses (every request
+                # of the row addresses the same: the child's output legs are among p's)
+                rep_ = sparse[p][2]
+                at = [sparse[c][1][rep_] * (t.size // sparse[c][0]) if c in sparse
+                      else pick_request_rows(root_order, pick[rep_], t)[0] for c, t in ((l, tl), (r, tr))]
+                dense_p = tuple(ix for ix in p_inds if ix not in root_order)
+                steps_new = [build_pick_rows_step(size_dict, tl, tr, dense_p, frozenset(root_order), sparse[p][0],
+                                                  at[0], at[1], factory, node=p)]
             elif steps_new is None or steps_new[0].kind == KIND_PAIR:
                 steps_new = (steps_new or []) + [build_pair_step(
                     dtype,

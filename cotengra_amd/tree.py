@@ -1069,15 +1069,22 @@ class ContractionTree:
 
         return _tree_contractor(self, order).topk(*arrays, k=k, **kwargs)
 
-    def contract_pick(self, arrays, coords=None, indices=None, order=None, **kwargs):
+    def contract_pick(self, arrays, coords=None, indices=None, order=None, chain=False, **kwargs):
         """Only the requested members of :meth:`contract`'s result -- ``coords`` ``(M, len(output))`` or
         ``indices`` ``(M,)`` flat positions in ``gathered_shape()``, as ``contract_sample`` / ``contract_topk``
         return them -- through a sparse root step: the ``(M,)`` amplitudes in the caller's order, summed over
         all slices; the full output never exists (``HipContractor.pick``; ``kwargs``: ``strip_exponent``,
-        ``check_zero``).  No output index may be sliced.  Not differentiable."""
+        ``check_zero``).  No output index may be sliced.  Not differentiable.
+
+        ``chain`` (``True``, or an ``int``: at most that many levels below the root): the requests are carried
+        down the tree -- a node below the root whose output legs the table addresses at few distinct projections
+        (``plan.pick_chain_nodes``: ``PICK_CHAIN_GAIN * M_c <= O_c``, its parent sparse too) is stored as ``M_c`` rows
+        of its other legs and computed by one row-sparse step, so cost and memory follow the
+        table, not ``2^k``.  Which nodes are sparse depends on the table through that rule: a request's bits are
+        therefore independent of the table's order and of duplicates, but not of which other requests are present."""
         from .contractor import _tree_contractor
 
-        return _tree_contractor(self, order).pick(*arrays, coords=coords, indices=indices, **kwargs)
+        return _tree_contractor(self, order).pick(*arrays, coords=coords, indices=indices, chain=chain, **kwargs)
 
     def contract_marginal(self, arrays, keep, order=None, **kwargs):
         """:meth:`contract` followed by the marginal of ``|result|^2`` over the output indices ``keep`` (a

@@ -100,7 +100,19 @@ enum {
  * and the plan's result is the vector of the requests (result_elems = R).  ctg_plan_create rejects code 2 on any
  * other kind of record, with other extents, or with a row, k or n table absent (offset -1) (CTG_E_INVALID), and checks the per-request tables like every table
  * (sum of the table maxima per operand inside its space).  The step launches alone, carries the slices of a
- * batch like every thread-per-output step, and takes strip_exponent / check_zero like every pair step. */
+ * batch like every thread-per-output step, and takes strip_exponent / check_zero like every pair step.
+ *
+ * Likewise added to ABI 10 without a bump: kernel code 3 in word 1 of a pair record -- the step of a row-sparse node
+ * below the root of a chained pick plan (compile_tree(pick=..., pick_chain=...), csrc/ctg_pick_rows.hip, DESIGN.md
+ * section 14).  Such a record has Bt = 1 and the tables of a thread-per-output pair step; its R = rows * row_lo rows
+ * are the rows of the node (the `hi` level of the three row tables: per row the offset of its sub-tensor in A, in B
+ * and in the result) times the row_lo dense positions A carries (the `lo` level), the n tables running over the N
+ * positions only B carries,
+ *   C[rowC.hi[m] + rowC.lo[i] + nC[n]] = alpha * sum_k A[rowA.hi[m] + rowA.lo[i] + kA(k)]
+ *                                                      * B[rowB.hi[m] + rowB.lo[i] + kB(k) + nB[n]].
+ * ctg_plan_create rejects code 3 on any other kind of record, with Bt != 1, or with a row, k or n table absent
+ * (CTG_E_INVALID), and checks the per-row tables like every table.  The step launches alone and carries the slices
+ * of a batch in gridDim.y. */
 typedef struct ctg_plan_desc {
     int32_t dtype;                /* CTG_F32 .. CTG_C128 */
     int64_t n_inputs;
@@ -313,7 +325,11 @@ int ctg_exec_profile_slice(ctg_exec* exec, int64_t slice_id, float* ms);
  * (two launches: the partial sums and the pass that adds them, a wavefront per
  * output when <true>).  The sparse root step of a pick plan (kernel code 2) is
  *   "pair_pick_kernel<float|double|c64|c128,VEC,SEG>"        VEC 1 | 2 adjacent k per load, SEG lanes per request
- * or, few requests under a very long contraction, one of the two k-reduction names above.  Match by prefix. */
+ * or, few requests under a very long contraction, one of the two k-reduction names above.  A row-sparse step
+ * below the root (kernel code 3) is
+ *   "pair_pick_rows_kernel<float|double|c64|c128,VEC>"       vector form, VEC 1 | 2 adjacent k per load
+ *   "pair_pick_rows_mfma_kernel<c64>"                        matrix-core form (row_lo >= 32, N >= 8, K >= 8)
+ * Match by prefix. */
 int ctg_exec_step_kernel(ctg_exec* exec, int64_t step, char* buf, int64_t buflen);
 
 int ctg_exec_sync(ctg_exec* exec);
