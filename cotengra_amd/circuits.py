@@ -370,3 +370,70 @@ def linear_xeb(n_qubits, probabilities):
     if p.size == 0:
         raise ValueError("linear_xeb of no samples.")
     return float(2.0 ** int(n_qubits) * p.mean() - 1.0)
+
+
+# ---------------------------------------------------------------------------------------------------- #
+# reduced density matrices of a (conditional) state: entanglement entropy, purity, correlators
+# ---------------------------------------------------------------------------------------------------- #
+
+
+def reduced_density_matrix(n, gates, qubits, fixed=None, optimize="greedy", dtype="complex64", target_size=None):
+    """The reduced density matrix of ``qubits`` in the output state of the ``n``-qubit circuit ``gates``: every
+    qubit not in ``fixed`` (a dict ``{qubit: 0 | 1}``: qubits projected onto that bit) stays open, so the result
+    tensor is the -- conditional, for a non-empty ``fixed`` -- state, and the partial trace over the open qubits
+    outside ``qubits`` is taken on the device (``ContractionTree.contract_rdm``); only the
+    ``2^k x 2^k`` matrix comes back.  At most 6 qubits.
+
+    Returns ``(rho, norm)``: ``rho`` of trace 1, rows and columns row-major over ``qubits`` in the order given, and
+    ``norm`` = ``sum |amplitude|^2`` of the open qubits (the probability of the fixed bits; 1 without any).
+    ``ValueError`` for an empty, repeated or out-of-range qubit list (as for ``sample_chaotic``'s marginal qubits),
+    a fixed qubit among ``qubits``, a fixed value other than 0 / 1, and a state of norm zero."""
+    from .interface import array_contract_tree
+
+    qs = [int(q) for q in qubits]
+    _check_marginal(n, qs)
+    fixed = {int(q): int(b) for q, b in (fixed or {}).items()}
+    for q, b in fixed.items():
+        if q < 0 or q >= n:
+            raise ValueError(f"fixed: qubit {q} outside the {n} qubits.")
+        if b not in (0, 1):
+            raise ValueError(f"fixed: qubit {q} is projected onto {b}; 0 or 1 is expected.")
+        if q in qs:
+            raise ValueError(f"qubit {q} is both fixed and kept.")
+    template = "".join(str(fixed[q]) if q in fixed else "?" for q in range(n))
+    open_qubits = [q for q in range(n) if q not in fixed]
+    inputs, output, size_dict, arrays = circuit_to_network(n, gates, template, simplify=True, dtype=dtype)
+    tree = array_contract_tree(inputs, output, size_dict, optimize=optimize)
+    if [tuple(t) for t in tree.inputs] != [tuple(t) for t in inputs] or tuple(tree.output) != tuple(output):
+        raise ValueError("optimize: the tree is not over this circuit's network.")
+    if target_size is not None:
+        tree = tree.slice(target_size=target_size)
+    label = dict(zip(open_qubits, output))   # (one output index per open qubit, in qubit order)
+    res = tree.contract_rdm(arrays, [label[q] for q in qs])
+    if not res.norm > 0:
+        raise ValueError("reduced_density_matrix: the state has norm zero.")
+    return res.rho / res.norm, res.norm
+
+
+def _spectrum(rho):
+    """Eigenvalues of the trace-normalised Hermitian matrix ``rho``, those below 0 from rounding clipped."""
+    rho = np.asarray(rho)
+    if rho.ndim != 2 or rho.shape[0] != rho.shape[1]:
+        raise ValueError(f"rho of shape {rho.shape}; a square matrix is expected.")
+    tr = float(np.trace(rho).real)
+    if not tr > 0:
+        raise ValueError("rho has no positive trace.")
+    return np.clip(np.linalg.eigvalsh(rho / tr), 0.0, None)
+
+
+def purity(rho):
+    """``trace(rho^2)`` of the trace-normalised ``rho``: 1 for a pure state, ``1 / D`` for the maximally mixed one."""
+    w = _spectrum(rho)
+    return float(np.sum(w * w))
+
+
+def von_neumann_entropy(rho, base=2):
+    """``-trace(rho log rho)`` of the trace-normalised ``rho`` in units of ``log(base)`` (bits by default)."""
+    w = _spectrum(rho)
+    w = w[w > 0]
+    return float(-np.sum(w * np.log(w)) / np.log(base))

@@ -249,6 +249,17 @@ class MarginalResult(collections.namedtuple("MarginalResult", "p norm exponent")
     __slots__ = ()
 
 
+class RdmResult(collections.namedtuple("RdmResult", "rho dims norm exponent")):
+    """What ``HipContractor.rdm`` returns: ``rho`` the ``(D, D)`` reduced density matrix of the kept output indices
+    (complex128, float64 for a real contraction), rows and columns row-major over the labels in the order the caller
+    named them, exactly Hermitian and NOT normalised (a list of such matrices for a list of requests); ``dims`` the
+    kept extents in that order (a list of tuples for a list of requests); ``norm`` = ``sum |x|^2`` of the whole
+    result = ``trace(rho)`` up to rounding; the base-10 ``exponent`` taken out under ``strip_exponent`` (0.0
+    otherwise: true values are ``rho 10^(2 exponent)``)."""
+
+    __slots__ = ()
+
+
 def _marginal_requests(tree, keep):
     """``keep`` of ``HipContractor.marginal`` as ``(several?, [(labels, keep flags per output axis, shape in the
     tensor's order, permutation to the caller's order), ...])`` -- host only; ``ValueError`` for a label that is
@@ -404,7 +415,7 @@ class HipContractor:
         # be multi-threaded (presets.py:77-88): upload -> run -> fetch is one critical section.
         self._lock = threading.RLock()
         # (executor state, strip_exponent) of the call made last if it left the whole contraction in the result
-        # tensor (__call__, sample, topk, marginal), None after anything else: what reuse=True reads (under _lock)
+        # tensor (__call__, sample, topk, marginal, rdm), None after anything else: what reuse=True reads (under _lock)
         self._reusable = None
 
     # ------------------------------------------------------------------ #
@@ -879,7 +890,7 @@ class HipContractor:
         the result dtype (a torch tensor for ROCm torch inputs); with ``strip_exponent`` ``(mantissa,
         exponent)`` as a call does.  ``M = 0``: an empty array, the device is not touched.  ``ValueError`` --
         before the device is touched -- for what :func:`pick_requests` refuses.  The result tensor of this
-        contractor is not touched, but ``reuse=True`` of :meth:`topk` / :meth:`marginal` refuses to read it after
+        contractor is not touched, but ``reuse=True`` of :meth:`topk` / :meth:`marginal` / :meth:`rdm` refuses to read it after
         a pick.  Not differentiable.
 
         ``chain`` (``True``, or an ``int``: at most that many levels below the root): the requests are carried
@@ -905,7 +916,7 @@ class HipContractor:
             fn = self._pick_contractor(req, chain)
             return fn._contract(arrays, False, check_zero, strip_exponent)
 
-    # ---- top-k and marginals of the result on the device (csrc/ctg_reduce.hip) ------------------ #
+    # ---- top-k, marginals and reduced density matrices of the result on the device -------- #
 
     def _reduce_state(self, arrays, strip_exponent, check_zero, reuse):
         """Under the lock: the executor state whose result tensor holds the whole contraction, and whether it was
@@ -935,7 +946,7 @@ class HipContractor:
         (``ctg_exec_result_topk``).  Returns a :class:`TopKResult`.  With
         ``strip_exponent`` the amplitudes, ``p``, ``norm`` and ``sum_p2`` are the mantissa's.  ``reuse=True``
         (no arrays): read the result tensor left by the call made directly before on this contractor
-        (``__call__``, ``sample``, ``topk`` or ``marginal``; its ``strip_exponent`` applies) instead of
+        (``__call__``, ``sample``, ``topk``, ``marginal`` or ``rdm``; its ``strip_exponent`` applies) instead of
         contracting again; ``RuntimeError`` when there is none or another call came between.  ``ValueError`` for
         ``k < 1`` or above the number of elements or 2^20, and when the result holds a NaN or inf.  An all-zero
         result is no error.  Not differentiable."""
@@ -978,6 +989,37 @@ class HipContractor:
             norm = ex.sample_info()[0]
             exponent = ex.get_exponent()[0] if strip else 0.0
         return MarginalResult(p=outs if several else outs[0], norm=norm, exponent=exponent)
+
+    def rdm(self, *arrays, keep, strip_exponent=False, check_zero=False, reuse=False):
+        """Contract (all slices, as a call does) and return the reduced density matrix of the output indices
+        ``keep`` -- ``rho[a, b] = sum over r of x[a, r] conj(x[b, r])``, ``r`` over every other output index, every
+        product and sum in double with a fixed order, on the device (``ctg_exec_result_rdm``, DESIGN.md section
+        15).  ``keep``: as for :meth:`marginal` -- a sequence of output index labels, or a list of such sequences
+        (several matrices of one contraction; ``rho`` and ``dims`` are lists then).  Rows and columns are row-major
+        over the labels in the order they were named; no label: the ``(1, 1)`` matrix ``sum p``.  Returns an
+        :class:`RdmResult`.  ``ValueError`` -- before the device is touched -- for a label that is unknown, not an
+        output index, or repeated, and for kept extents whose product exceeds 64.  ``reuse=True``: as for
+        :meth:`topk`.  Not differentiable."""
+        several, reqs = _marginal_requests(self.tree, keep)
+        shape = tuple(self.tree.gathered_shape())
+        for labels, flags, kshape, perm in reqs:
+            runtime.rdm_dim(shape, flags)
+        if reuse and arrays:
+            raise ValueError("reuse=True reads the result of the call before: give no arrays.")
+        with self._lock:
+            st, strip = self._reduce_state(arrays, strip_exponent, check_zero, reuse)
+            ex = st["exec"]
+            rhos, dims = [], []
+            for labels, flags, kshape, perm in reqs:
+                rho = ex.rdm_result(shape, flags)
+                d = rho.shape[0]
+                # rows and columns from the tensor's order of the kept axes to the caller's
+                rho = rho.reshape(kshape + kshape).transpose(perm + tuple(len(perm) + p for p in perm))
+                rhos.append(np.array(rho.reshape(d, d), order="C"))
+                dims.append(tuple(kshape[p] for p in perm))
+            norm = ex.sample_info()[0]
+            exponent = ex.get_exponent()[0] if strip else 0.0
+        return RdmResult(rho=rhos if several else rhos[0], dims=dims if several else dims[0], norm=norm, exponent=exponent)
 
     def profile(self, arrays, slice_id=0):
         """Per-step milliseconds for one slice (see ``Plan.describe_steps``)."""

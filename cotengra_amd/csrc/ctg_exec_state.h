@@ -195,6 +195,30 @@ hipError_t launch_range_hist(const void* x, int64_t n, void* partials, int64_t b
                              hipStream_t stream);
 }
 
+namespace ctg {
+// (ctg_reduce.hip) What the host decides about a marginal -- or a reduced density matrix (ctg_rdm.hip), which splits the
+// axes the same way -- before anything is launched: size-1 axes dropped, adjacent axes of equal keep status merged;
+// the route; the keep bitmask of the power-of-two route; extents and strides of the kept / dropped axes otherwise.
+constexpr int kMargMaxAxes = 32;                 // merged axes of one keep status (extents >= 2: 2^31 elements each way)
+constexpr int64_t kReduceMaxElems = 1ll << 40;   // (a workgroup's 32-bit counts hold its share of a digit pass)
+struct MargAxes {
+    int nk, nd;
+    int64_t kext[kMargMaxAxes], kstr[kMargMaxAxes], dext[kMargMaxAxes], dstr[kMargMaxAxes];
+};
+struct MarginalPlan {
+    int64_t n = 1, m = 1, rc = 1;
+    bool fast = false;
+    int64_t mask = 0;
+    MargAxes ax{};
+};
+// CTG_OK, or CTG_E_INVALID with *why set
+__attribute__((visibility("hidden"))) int marginal_plan(int64_t rank, const int64_t* extents, const int32_t* keep,
+                                                        int64_t result_elems, MarginalPlan* out, const char** why);
+// the executor's scratch of ctg_reduce.hip / ctg_rdm.hip (d_reduce), at least `want` bytes; the stream must be idle
+// (the statistics call synchronised it).  CTG_OK, CTG_E_NOMEM or CTG_E_HIP with the error set.
+__attribute__((visibility("hidden"))) int reduce_reserve(ctg_exec* e, int64_t want);
+}
+
 // LDS-resident subtrees (ctg_lds_host.hip): descriptor validation (host only) and per-executor packing
 __attribute__((visibility("hidden"))) int ctg_lds_validate(const ctg_plan* p);
 __attribute__((visibility("hidden"))) int ctg_lds_build(ctg_exec* e);

@@ -58,10 +58,8 @@ constexpr int kBins = 1 << kDigitBits;
 constexpr int kHistMaxGrid = 1024;            // workgroups of a digit pass
 constexpr int kSelThreads = 1024;
 constexpr int64_t kTopkCompact = 1 << 16;     // finish on a compact list once the class holds at most this many keys
-constexpr int64_t kReduceMaxElems = 1ll << 40;   // (a workgroup's 32-bit counts hold its share of a digit pass)
 constexpr int kMargChunk = 64;                // blocks per (output, chunk) of the fast route
 constexpr int64_t kMargGeneralChunk = 1024;   // complement positions per work item of the general route
-constexpr int kMargMaxAxes = 32;              // merged axes of one keep status (extents >= 2: 2^31 elements each way)
 
 // {prefix chosen so far, k still to find inside its class, size of the class, elements above the class}
 struct TopkState {
@@ -482,11 +480,6 @@ __global__ __launch_bounds__(kSampleThreads) void marg_sum_kernel(const double* 
     out[j] = accumulate ? out[j] + s : s;
 }
 
-struct MargAxes {
-    int nk, nd;
-    int64_t kext[kMargMaxAxes], kstr[kMargMaxAxes], dext[kMargMaxAxes], dstr[kMargMaxAxes];
-};
-
 // Work item (output j, chunk ch): B[ch m + j] <- p at the complement positions ch chunk ... of output j, serially
 template <typename T>
 __global__ __launch_bounds__(kSampleThreads) void marg_general_kernel(const T* __restrict__ x, MargAxes ax, int64_t m,
@@ -548,18 +541,7 @@ int rfail(int code, const char* fmt, ...) {
 
 int64_t up256(int64_t b) { return (b + 255) & ~(int64_t)255; }
 
-// the executor's scratch of this file, at least `want` bytes (the stream is idle: the statistics call synchronised it)
-int reserve(ctg_exec* e, int64_t want) {
-    if (e->reduce_bytes >= want) return CTG_OK;
-    if (e->d_reduce) {
-        HIP_TRY_R(hipFree(e->d_reduce));
-        e->d_reduce = nullptr;
-        e->reduce_bytes = 0;
-    }
-    HIP_TRY_R(hipMalloc(&e->d_reduce, (size_t)want));
-    e->reduce_bytes = want;
-    return CTG_OK;
-}
+int reserve(ctg_exec* e, int64_t want) { return reduce_reserve(e, want); }
 
 // sum p of the result by the statistics passes of ctg_sample.hip (synchronises): CTG_E_NORM unless finite
 int check_norm(ctg_exec* e, const char* what) {
@@ -717,16 +699,21 @@ int marginal_general(ctg_exec* e, const MargAxes& ax, int64_t m, int64_t rc, dou
 
 }  // namespace
 
-// What the host decides about a marginal before anything is launched: size-1 axes dropped, adjacent axes of equal
-// keep status merged; the route; the bitmask of the power-of-two route; extents and strides for the general one.
+// marginal_plan and reduce_reserve of ctg_exec_state.h (ctg_rdm.hip shares them)
 namespace ctg {
 
-struct MarginalPlan {
-    int64_t n = 1, m = 1, rc = 1;
-    bool fast = false;
-    int64_t mask = 0;
-    MargAxes ax{};
-};
+// the executor's scratch of this file, at least `want` bytes (the stream is idle: the statistics call synchronised it)
+int reduce_reserve(ctg_exec* e, int64_t want) {
+    if (e->reduce_bytes >= want) return CTG_OK;
+    if (e->d_reduce) {
+        HIP_TRY_R(hipFree(e->d_reduce));
+        e->d_reduce = nullptr;
+        e->reduce_bytes = 0;
+    }
+    HIP_TRY_R(hipMalloc(&e->d_reduce, (size_t)want));
+    e->reduce_bytes = want;
+    return CTG_OK;
+}
 
 // CTG_OK, or CTG_E_INVALID with *why set
 int marginal_plan(int64_t rank, const int64_t* extents, const int32_t* keep, int64_t result_elems, MarginalPlan* out,

@@ -1,6 +1,7 @@
 // ctg_sample_elem.h -- p = |x|^2 of one element of the result tensor and the 16-byte loads that feed it: shared by
 // the kernels that reduce p over the result (ctg_sample.hip: statistics and draws; ctg_reduce.hip: top-k and
-// marginals), so that every one of them forms the same double for the same element.
+// marginals), so that every one of them forms the same double for the same element.  ctg_rdm.hip (reduced density
+// matrices) takes the same loads without the square (load_group).
 #pragma once
 
 #include <cstdint>
@@ -61,6 +62,24 @@ __device__ __forceinline__ void load_group_p(const T* __restrict__ x, int64_t e,
     } else {
 #pragma unroll
         for (int k = 0; k < V; ++k) p[k] = (e + k < n) ? SampleElem<T>::p(x[e + k]) : 0.0;
+    }
+}
+
+// The V elements themselves, for the kernels that need more than p (ctg_rdm.hip); elements at or past n are zero.
+template <typename T>
+__device__ __forceinline__ void load_group(const T* __restrict__ x, int64_t e, int64_t n, bool vec, T (&v)[16 / sizeof(T)]) {
+    constexpr int V = 16 / sizeof(T);
+    if (vec && e + V <= n) {
+        union {
+            uint4 raw;
+            T v[V];
+        } g;
+        g.raw = *reinterpret_cast<const uint4*>(x + e);
+#pragma unroll
+        for (int k = 0; k < V; ++k) v[k] = g.v[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k) v[k] = (e + k < n) ? x[e + k] : T{};
     }
 }
 

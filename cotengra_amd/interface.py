@@ -242,6 +242,15 @@ class ContractExpression:
         self._after_reduce()
         return out
 
+    def rdm(self, *arrays, keep, **kwargs):
+        """``expr(*arrays)`` followed by the reduced density matrix of the output indices ``keep`` on the device
+        (``HipContractor.rdm``); the expression's own ``strip_exponent`` / ``check_zero`` unless given."""
+        kwargs.setdefault("strip_exponent", self.fn.strip_exponent)
+        kwargs.setdefault("check_zero", self.fn.check_zero)
+        out = self.fn.rdm(*arrays, keep=keep, **kwargs)
+        self._after_reduce()
+        return out
+
     def device_bytes(self):
         """Device memory this expression's executors hold right now (``ctg_exec_device_bytes``:
         arena x slice batch, inputs, tables, result, scratch), read under the contractor's lock

@@ -50,6 +50,7 @@ SYMBOLS = (
     "ctg_exec_range_audit",
     "ctg_exec_result_topk",
     "ctg_exec_result_marginal",
+    "ctg_exec_result_rdm",
     "ctg_exec_download_result",
     "ctg_exec_download_arena",
     "ctg_exec_get_state",
@@ -165,6 +166,7 @@ def load():
         "ctg_exec_range_audit": [vp, C.c_int64, i64p, C.POINTER(C.c_double)],
         "ctg_exec_result_topk": [vp, C.c_int64, i64p, vp, C.POINTER(C.c_double)],
         "ctg_exec_result_marginal": [vp, C.c_int64, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_double)],
+        "ctg_exec_result_rdm": [vp, C.c_int64, i64p, C.POINTER(C.c_int32), vp],
         "ctg_exec_download_result": [vp, vp],
         "ctg_exec_download_arena": [vp, C.c_int64, C.c_int64, vp],
         "ctg_exec_get_state": [vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_int)],
@@ -229,6 +231,36 @@ def check_topk_k(k):
     if k < 1:
         raise ValueError(f"k = {k}: need at least 1.")
     return k
+
+
+def rdm_dim(extents, keep):
+    """``D``, the product of the kept extents of a reduced-density-matrix request: ``ValueError`` for an extent below
+    1 and for ``D`` above ``Executor.RDM_MAX_DIM`` -- host only, before any device work."""
+    d = 1
+    for n, f in zip(extents, keep):
+        if n < 1:
+            raise ValueError(f"extent {n} is not positive.")
+        if f == 1:
+            d *= int(n)
+    if d > Executor.RDM_MAX_DIM:
+        raise ValueError(f"rdm: the kept extents' product is {d}; at most {Executor.RDM_MAX_DIM} (CTG_RDM_MAX_DIM).")
+    return d
+
+
+def rdm_variant(dtype, extents, keep):
+    """The kernel ``ctg_exec_result_rdm`` chooses for a result of ``dtype`` and shape ``extents`` with the axes
+    ``keep`` kept -- a function of those alone (csrc/ctg_rdm.hip): ``"rdm_chunk_kernel<T,NT>"`` on the power-of-two
+    route (every extent a power of two, at least 4096 elements; ``NT = max(D, 16) / 16``), ``"rdm_general_kernel<T>"``
+    otherwise; ``T`` one of ``float``, ``double``, ``c64``, ``c128``."""
+    t = {"float32": "float", "float64": "double", "complex64": "c64", "complex128": "c128"}[np.dtype(dtype).name]
+    ext = [int(n) for n in extents]
+    d = rdm_dim(ext, list(keep))
+    n = 1
+    for v in ext:
+        n *= v
+    if n >= 4096 and all(v & (v - 1) == 0 for v in ext):
+        return f"rdm_chunk_kernel<{t},{max(d, 16) // 16}>"
+    return f"rdm_general_kernel<{t}>"
 
 
 class DevicePlan:
@@ -506,6 +538,31 @@ class Executor:
         _check(load().ctg_exec_result_marginal(self.handle, ext.size, _i64p(ext), kp.ctypes.data_as(C.POINTER(C.c_int32)),
                                                out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
+
+    # -- reduced density matrices of the result tensor (csrc/ctg_rdm.hip) -- #
+
+    RDM_MAX_DIM = 64   # CTG_RDM_MAX_DIM
+
+    def rdm_result(self, extents, keep):
+        """``rho[a, b] = sum over r of x[a, r] conj(x[b, r])`` of the result tensor (``ctg_exec_result_rdm``): ``a``,
+        ``b`` over the axes with ``keep[a] = 1``, ``r`` over the others; ``extents`` is the shape of the result.  A
+        ``(D, D)`` complex128 array (float64 for a real plan), rows and columns row-major over the kept axes in the
+        tensor's own order; exactly Hermitian.  ``ValueError`` for what ``marginal_result`` refuses, for ``D`` above
+        ``RDM_MAX_DIM`` (nothing is launched) and for a result whose ``sum p`` is not finite."""
+        ext = np.ascontiguousarray(extents, dtype=np.int64).reshape(-1)
+        kp = np.ascontiguousarray(keep, dtype=np.int32).reshape(-1)
+        if ext.size != kp.size:
+            raise ValueError(f"{ext.size} extents and {kp.size} keep entries.")
+        d = rdm_dim(ext.tolist(), kp.tolist())
+        cplx = np.dtype(self.plan.dtype).kind == "c"
+        out = np.empty((d, d), dtype=np.complex128 if cplx else np.float64)
+        _check(load().ctg_exec_result_rdm(self.handle, ext.size, _i64p(ext), kp.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          C.c_void_p(out.ctypes.data)))
+        return out
+
+    def rdm_variant(self, extents, keep):
+        """The name of the kernel ``rdm_result(extents, keep)`` runs on this executor (:func:`rdm_variant`)."""
+        return rdm_variant(self.plan.dtype, extents, keep)
 
     # -- range audit (csrc/ctg_range.hip, cotengra_amd/rangeaudit.py) -- #
 

@@ -1094,6 +1094,14 @@ class ContractionTree:
 
         return _tree_contractor(self, order).marginal(*arrays, keep=keep, **kwargs)
 
+    def contract_rdm(self, arrays, keep, order=None, **kwargs):
+        """:meth:`contract` followed by the reduced density matrix of the output indices ``keep`` (a sequence of
+        labels, or a list of such sequences) on the device (``HipContractor.rdm``; ``kwargs``: ``strip_exponent``,
+        ``check_zero``, ``reuse``).  Not differentiable."""
+        from .contractor import _tree_contractor
+
+        return _tree_contractor(self, order).rdm(*arrays, keep=keep, **kwargs)
+
     def contract_audit(self, arrays, slices=(0,), order=None):
         """Range audit of the contraction on ``arrays`` (``HipContractor.audit``): the
         slices ``slices`` run step by step, one record per plan step with the exponent statistics of its

@@ -273,8 +273,8 @@ int ctg_exec_run_share(ctg_exec* exec, int64_t rank, int64_t world, int64_t unit
 /* ABI 4.  Device memory this executor holds right now: inputs space, arena x slice batch,
  * tables, the result if it owns it, the scratch buffer if the plan has a step that needs one
  * (allocated by ctg_exec_create), the scratch of ctg_exec_result_stats / ctg_exec_sample_result once they
- * have run (ABI 9), of ctg_exec_range_audit and of ctg_exec_result_topk / ctg_exec_result_marginal likewise
- * (ABI 10).  What a cache of contractors -- the reference keeps them
+ * have run (ABI 9), of ctg_exec_range_audit and of ctg_exec_result_topk / ctg_exec_result_marginal / ctg_exec_result_rdm
+ * likewise (ABI 10).  What a cache of contractors -- the reference keeps them
  * on the tree, core.py:3708-3722 -- has to count against its budget. */
 int ctg_exec_device_bytes(ctg_exec* exec, int64_t* bytes);
 /* ABI 5.  Is there a kernel instantiation for a three-step tile of this shape (stem steps fused
@@ -426,6 +426,38 @@ int ctg_exec_result_topk(ctg_exec* exec, int64_t k, int64_t* idx, void* elems, d
  * and at most 2 * 8 * CTG_MARGINAL_PARTIALS bytes (general route: 8 bytes per 512 elements instead). */
 #define CTG_MARGINAL_PARTIALS (1 << 22)
 int ctg_exec_result_marginal(ctg_exec* exec, int64_t rank, const int64_t* extents, const int32_t* keep, double* out);
+/* Added to ABI 10 WITHOUT a bump of CTG_ABI_VERSION likewise (one new symbol; a binding that needs it looks it up): the
+ * reduced density matrix of the kept axes of the result tensor on the device (csrc/ctg_rdm.hip),
+ *   rho[a, b] = sum over r of x[a, r] * conj(x[b, r]),
+ * a, b over the kept axes, r over all the others.  extents[rank] and keep[a] in {0, 1} are those of
+ * ctg_exec_result_marginal, which returns the diagonal of this matrix.  D = the product of the kept extents,
+ * t = result_elems / D: out holds D * D elements, row-major -- double2 {re, im} for complex plans, double for real
+ * plans (rho is real symmetric there) -- rows and columns row-major over the kept axes in the tensor's own order.
+ * No kept axis: D = 1, out = sum p; all axes kept: t = 1, out = x x^dagger.  The tensor is read as the two calls
+ * above read it (whoever owns the memory, the mantissa under strip_exponent, after the stream's earlier work, after
+ * the statistics passes, which run first); the stream is synchronised.  CTG_E_NORM when sum p is not finite; an
+ * all-zero tensor gives a zero matrix.  CTG_E_INVALID for everything ctg_exec_result_marginal refuses, a null out, and
+ * D > CTG_RDM_MAX_DIM -- checked on the host before anything is launched.
+ *   - The result is exactly Hermitian: only b <= a is computed, the other half is written as its conjugate, and
+ *     Im rho[a, a] is exactly 0.0.
+ *   - No floating-point atomics.  Every grid and every association of a sum is a function of (extents, keep) alone:
+ *     the same bytes give the same bits on every run and every executor.
+ *   - Every product is formed in fp64 -- exact for float / complex64 plans, rounded once for double plans -- and every
+ *     sum is in fp64: per real component |rho[a,b] - exact| <= (m + 1) 2^-53 sqrt(rho[a,a] rho[b,b]) with m = 2t
+ *     (complex) or t (real) products.
+ * Every extent a power of two and at least 4096 elements: chunks of 4096 elements (all rows -- 16 at least: for D < 16
+ * low bits of r are folded into the row and summed out at the end -- by 4096 / rows consecutive values of r), widened
+ * to fp64 in LDS and multiplied by v_mfma_f64_16x16x4_f64 on the 16 x 16 tiles of the lower triangle; a workgroup takes
+ * the chunks wg, wg + grid, ... in ascending order, grid = min(512, ceil(chunks / 3)); the workgroups' partial sums are
+ * added in ascending order in groups of 32, then the groups.  The kernel is "rdm_chunk_kernel<T,NT>", T in
+ * float | double | c64 | c128, NT = max(D, 16) / 16 in 1 | 2 | 4.  Any other shape: "rdm_general_kernel<T>", a serial
+ * walk per (a, b <= a, chunk of max(1024, ceil(t / 1024)) values of r), the chunks added in ascending order; not
+ * tuned.  Scratch: the buffer of the two calls above (counted by ctg_exec_device_bytes, freed by ctg_exec_destroy):
+ * 16 D^2 bytes for the output, and at most 512 * 40 KiB of partial sums + 16 * 40 KiB of group sums (21 MiB;
+ * general route: at most 1024 * 16 D^2 bytes, 64 MiB).  Not differentiable.  No multi-rank entry: after
+ * ctg_exec_reduce the root's result tensor holds the total and the call works there (untested). */
+#define CTG_RDM_MAX_DIM 64
+int ctg_exec_result_rdm(ctg_exec* exec, int64_t rank, const int64_t* extents, const int32_t* keep, void* out);
 /* debugging aid: copy `n` elements of the arena starting at element `offset`
  * to the host (synchronous) */
 int ctg_exec_download_arena(ctg_exec* exec, int64_t offset, int64_t n, void* host_out);
