@@ -233,8 +233,10 @@ def random_stem(seed):
     return stem_network(nq, gates, seed, sliced=int(rng.integers(0, 3)))
 
 
-# (nq, gates): every instantiation of the fused kernel -- 16 / 32 columns on either step,
-# 256 and 512 tile rows, K up to 128, N2 up to 128 -- and chains with leftovers
+# (nq, gates): the families of the fused kernel -- 16 / 32 columns on either step, 256 and 512 tile rows, K up to 128,
+# N2 up to 128 -- and chains with leftovers.  NOT every instantiation: these stems (with 0 and 2 indices sliced), ONE_CASES
+# and random_stem(0..47) together reach 19 of the 47 static fp32 pairs and 20 of the 38 16-bit geometries; one row per
+# instantiation, asserted by name, is tests/stem_variant_cases.py (run by tests/test_gpu_stem_variants.py)
 STEM_CASES = [
     (16, [(3, 3), (5, 5), (5, 5)]),                    # k32 n32 | k32 n32
     (16, [(3, 3), (4, 4), (5, 5)]),                    # k16 n16 | k32 n32: 16 columns first, 512 rows
