@@ -220,6 +220,9 @@ struct StemArgs {
     // the big operand as its producer recorded it, and where this launch records that of its result (device floats)
     const float* amax;
     float* cmax;
+    // the result's tables allow 16-byte stores of two adjacent columns (ctg_runtime.hip: stem_pair16_ok); which kernels
+    // use it: ctg_stem_impl.h, stem_pair16_shape
+    int32_t pair16;
 };
 
 // element offset of an operand for the slice-in-batch this block works on
@@ -597,6 +600,8 @@ bool stem2h_uses_h2(const StemArgs& p);   // does the step have a 16-bit instant
 bool stem2_uses_bf3(const StemArgs& p);   // the same question for launch_stem2 (bf16 x 3: records the result's largest element too)
 hipError_t launch_stem2h(const StemArgs& p, hipStream_t stream);
 void stem2h_kernel_name(const StemArgs& p, char* buf, size_t n);
+int stem2_last_paired();    // did the last launch_stem2 / launch_stem2h take the kernel with 16-byte stores (stem2[h]_kernel_p16)?
+int stem2h_last_paired();
 
 hipError_t launch_single(int dtype, const StepArgs& p, hipStream_t stream);
 bool pair_bf16x3_on(const StepArgs& p);   // (ctg_pair_mfma.hip) do long tiled steps multiply with bf16 x 3 products right now?

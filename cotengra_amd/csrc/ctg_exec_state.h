@@ -76,6 +76,7 @@ struct ctg_exec {
     int64_t plan_steps = 0;                // (= plan->n_steps, for smax_slot)
     std::vector<char> rec_wanted;          // the record of step s's largest |component| has a reader (build_hints)
     std::vector<char> wave_member;         // step s is launched inside a wave-front group (it never records its maximum)
+    std::vector<char> stem_paired_ran;     // step s last ran a kernel with paired 16-byte stores (ctg_exec_step_paired_stores)
     std::vector<char> stem_h2_ran;         // step s last ran in the fp16 x 2 arithmetic (its record is valid)
     std::vector<ctg::MfmaHints> hints;  // per step kernel hints (MFMA steps)
     // the same for launches that carry several slices (batch > 1): wider column tiles

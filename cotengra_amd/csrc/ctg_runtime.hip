@@ -195,6 +195,33 @@ int validate_stem(const ctg_plan* p, int64_t s) {
     return CTG_OK;
 }
 
+// May the stem pair of step s (validated: every table inside the blob) store its result 16 bytes at a time -- the two
+// columns 2 j, 2 j + 1 of a row in one store (ctg_stem_impl.h: stem2h_kernel_p16)?  The paired columns are exactly one
+// element apart, and everything else a store address is summed from is even: the left column of every pair, every
+// row, tile and slice offset, the result's place in its space and the stride of the replicas of a slice batch.  Read
+// off the step's own tables; the planner is not asked.
+bool stem_pair16_ok(const ctg_plan* p, int64_t s) {
+    const int64_t* r = &p->steps[s * STEP_WORDS];
+    const int64_t* h = &p->tables[r[W_STEM]];
+    if (h[SW_ONE] == 1 || h[SW_TRI] == 1) return false;
+    const int64_t N2 = h[SW_N2], rows2 = h[SW_ROWS2], n_tiles = h[SW_NTILES], g_lo = h[SW_GLO];
+    if (N2 < 2 || (N2 & 1)) return false;
+    const int64_t* oc = &p->tables[h[SW_TABS + ST_OUT_COL]];
+    for (int64_t j = 0; j < N2; j += 2)
+        if ((oc[j] & 1) || oc[j + 1] != oc[j] + 1) return false;
+    const int even_tabs[3] = {ST_OUT_ROW, ST_GC_HI, ST_GC_LO};
+    const int64_t len[3] = {rows2, n_tiles / g_lo, g_lo};
+    for (int t = 0; t < 3; ++t)
+        for (int64_t i = 0; i < len[t]; ++i)
+            if (p->tables[h[SW_TABS + even_tabs[t]] + i] & 1) return false;
+    if (r[W_C_OFF] & 1) return false;
+    if (r[W_C_SPACE] == SPACE_ARENA && (p->arena_elems & 1)) return false;   // (the replicas of a slice batch)
+    if (r[W_C_LEAF] >= 0)
+        for (int64_t j = 0; j < p->n_sliced; ++j)
+            if (p->slice_strides[r[W_C_LEAF] * p->n_sliced + j] & 1) return false;
+    return true;
+}
+
 int validate_plan(ctg_plan* p) {
     if (p->dtype < 0 || p->dtype > 3) return fail(CTG_E_INVALID, "bad dtype %d", p->dtype);
     if (p->n_inputs < 1) return fail(CTG_E_INVALID, "plan needs at least one input");
@@ -547,6 +574,7 @@ void resolve_args(ctg_exec* e) {
             q.bf3 = e->stem_bf16x3;
             q.a_elems = r[W_A_SIZE];
             q.c_elems = r[W_C_SIZE];
+            q.pair16 = stem_pair16_ok(p, s) && ((uintptr_t)q.C & 15) == 0 ? 1 : 0;
             const int64_t** tabs[ST_COUNT] = {&q.gA_hi, &q.gA_lo, &q.gC_hi, &q.gC_lo, &q.kj_a, &q.lane_a, &q.rt_a,
                                               &q.chunk_a, &q.b1_off, &q.b2_off, &q.mid_row, &q.mid_col,
                                               &q.out_row, &q.out_col};
@@ -1274,6 +1302,8 @@ int launch_step(ctg_exec* e, int64_t s, hipStream_t stream) {
                     q.amax = slot;
                 }
                 if (err == hipSuccess) err = h2 ? launch_stem2h(q, stream) : launch_stem2(q, stream);
+                // (which form of the kernel the launch took: ctg_exec_step_paired_stores)
+                if (err == hipSuccess) e->stem_paired_ran[s] = (char)(h2 ? stem2h_last_paired() : stem2_last_paired());
             }
             break;
         }
@@ -2069,6 +2099,7 @@ int ctg_exec_create(const ctg_plan* p, int device, void* stream, void* ext_resul
                 }
             }
             e->stem_h2_ran.assign(p->n_steps, 0);
+            e->stem_paired_ran.assign(p->n_steps, 0);
             if (e->wave_member.size() != (size_t)p->n_steps) e->wave_member.assign(p->n_steps, 0);
             (void)stems;
             if (p->dtype == CTG_C64) {   // (plans without a stem may still have long tiled steps)
@@ -2720,6 +2751,38 @@ int ctg_exec_step_kernel(ctg_exec* e, int64_t step, char* buf, int64_t buflen) {
         pair_valu_name(p->dtype, e->args[step], kScratchBytes, name, sizeof(name));
     }
     snprintf(buf, (size_t)buflen, "%s", name);
+    return CTG_OK;
+}
+
+int ctg_plan_stem_pair16(ctg_plan* p, int64_t step, int* ok) {
+    if (!p || !ok) return fail(CTG_E_INVALID, "null argument");
+    if (step < 0 || step >= p->n_steps) return fail(CTG_E_INVALID, "step out of range");
+    *ok = p->steps[step * STEP_WORDS + W_KIND] == KIND_STEM2 && stem_pair16_ok(p, step) ? 1 : 0;
+    return CTG_OK;
+}
+
+int ctg_exec_step_paired_stores(ctg_exec* e, int64_t step, int* paired) {
+    if (!e || !paired) return fail(CTG_E_INVALID, "null argument");
+    if (step < 0 || step >= e->plan->n_steps) return fail(CTG_E_INVALID, "step out of range");
+    // (what the step's last launch took, as the launcher itself recorded it)
+    *paired = (size_t)step < e->stem_paired_ran.size() && e->stem_paired_ran[step] ? 1 : 0;
+    return CTG_OK;
+}
+
+int ctg_exec_step_stem_max(ctg_exec* e, int64_t step, int64_t z, float* mx) {
+    if (!e || !mx) return fail(CTG_E_INVALID, "null argument");
+    const ctg_plan* p = e->plan;
+    if (step < 0 || step >= p->n_steps) return fail(CTG_E_INVALID, "step out of range");
+    if (z < 0 || z >= (e->batch > 1 ? e->batch : 1)) return fail(CTG_E_INVALID, "slice of the batch out of range");
+    if (e->d_stem_max == nullptr || (size_t)step >= e->stem_h2_ran.size() || !e->stem_h2_ran[step] ||
+        p->steps[step * STEP_WORDS + W_KIND] != KIND_STEM2)
+        return fail(CTG_E_INVALID, "step %lld has recorded no maximum", (long long)step);
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    float rec[kMaxSub];
+    HIP_TRY(hipMemcpy(rec, e->smax_slot(0, step, (e->invariant[step] || e->grouped[step]) ? 0 : z), sizeof(rec), hipMemcpyDeviceToHost));
+    *mx = rec[0];
+    for (int i = 1; i < kMaxSub; ++i) *mx = std::max(*mx, rec[i]);
     return CTG_OK;
 }
 

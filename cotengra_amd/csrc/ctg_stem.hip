@@ -5,8 +5,13 @@
 
 namespace ctg {
 #ifdef CTG_STEM_DEV_ONE
-template __global__ void stem2_kernel<CTG_STEM_DEV_ONE>(StemArgs);
+#ifdef CTG_STEM_DEV_P16   // (... its form with paired stores)
+template __global__ void stem2_kernel_p16<CTG_STEM_DEV_ONE>(StemArgs);
 #else
+template __global__ void stem2_kernel<CTG_STEM_DEV_ONE>(StemArgs);
+#endif
+#else
+int stem2_last_paired() { return stem_last_paired; }
 bool stem2_supported(const StemArgs& p) { return stem2_supported_shape(p); }
 bool stem3_supported(const StemArgs& p) { return stem3_supported_shape(p); }
 bool stem2_uses_bf3(const StemArgs& p) { return stem_uses_16bit(p); }

@@ -5,8 +5,13 @@
 
 namespace ctg {
 #ifdef CTG_STEM_DEV_ONE
-template __global__ void stem2h_kernel<CTG_STEM_DEV_ONE>(StemArgs);
+#ifdef CTG_STEM_DEV_P16   // (... its form with paired stores)
+template __global__ void stem2h_kernel_p16<CTG_STEM_DEV_ONE>(StemArgs);
 #else
+template __global__ void stem2h_kernel<CTG_STEM_DEV_ONE>(StemArgs);
+#endif
+#else
+int stem2h_last_paired() { return stem_last_paired; }
 bool stem2h_supported(const StemArgs& p) { return stem2_supported_shape(p); }
 bool stem2h_uses_h2(const StemArgs& p) { return stem_uses_16bit(p); }
 void stem2h_kernel_name(const StemArgs& p, char* buf, size_t n) { stem_kernel_name<Fp16x2>(p, buf, n); }

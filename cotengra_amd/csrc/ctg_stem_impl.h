@@ -22,7 +22,8 @@
 //            wants, whatever index permutation lies between the two steps;
 //   barrier
 //   step 2   work items (32-row tile, 32-column group) of the intermediate are
-//            multiplied by B2 and stored: 8 bytes per lane, 256 B runs.
+//            multiplied by B2 and stored: 8 bytes per lane, 256 B runs (16 bytes per lane and whole 512 B
+//            rows where a wave holds both column groups of a row tile: stem2h_kernel_p16 below).
 //
 // Complex on the real matrix cores, second formulation (the first one is in
 // ctg_pair_mfma.hip).  v_mfma_f32_32x32x2_f32: D(32x32) += A'(32x2) B'(2x32).  Here a
@@ -479,9 +480,11 @@ constexpr bool STEM_NT_STORES = CTG_STEM_NT_STORES != 0;
 constexpr bool STEM_GATHER_PORTIONS = CTG_STEM_GATHER_PORTIONS != 0;
 // AR: the arithmetic of the BF3 = true kernels (Bf16x3 / Fp16x2 above); the body of stem2_kernel / stem2h_kernel below.
 template <class AR, bool PACK1, bool PACK2, int RT1_, int CS1, int NCH, int IT2_, bool BR1, int K2Q, bool VEC, bool BF3,
-          bool RI2, bool ONE, int ITM, bool PACKM, bool XM, bool LM, bool WS>
+          bool RI2, bool ONE, int ITM, bool PACKM, bool XM, bool LM, bool WS, bool P16 = false>
 __device__ __forceinline__ void stem2_body(const StemArgs& p) {
     constexpr bool TRI = ITM > 0;
+    static_assert(!P16 || (XM && !PACK2 && NCH > 0 && ((WS && IT2_ == 1) || (!WS && IT2_ == 2))),
+                  "paired stores: a wave whose two items are the two column groups of a row tile");
     static_assert(!LM, "reserved (the limb intermediate was removed): kernel names stay 17 arguments long");
     static_assert(BF3 || !AR::fp16, "fp16 x 2: the 16-bit kernels only (its object has no fp32 products)");
     static_assert(!AR::fp16 || !TRI, "fp16 x 2: pairs and single steps");
@@ -944,6 +947,7 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
     // slice, of the gathers alone 6 % (profiles/r3_stem_knockout.txt).
     constexpr int NST = PACK2 ? 8 : 16;
     float2 pv[RI2 ? 1 : NST];
+    float2 pw[P16 ? NST : 1];   // P16: the second column group's values (the right-hand neighbours of pv's)
     float* pdst = C;
     // RI2: the accumulators of step 2, [set][complex rows 0-15 | 16-31]; the stores of an item read
     // them in place (registers 2 p, 2 p + 1 = Re, Im), so a set is left alone until its stores are
@@ -964,13 +968,26 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
             *(float2*)q = v;
         }
     };
+    // P16: two adjacent elements of a row, 16 bytes (the host has checked the alignment: stem_pair16_ok)
+    auto store4 = [&](float* q, float2 v, float2 w) __attribute__((always_inline)) {
+#ifdef CTG_STEM_BOUNDS
+        if ((uint64_t)((char*)q - (char*)C) + 16 > (uint64_t)p.c_elems * 8) {
+            atomicAdd(&ctg_stem_oob<AR>[1], 1ull);
+            return;
+        }
+#endif
+        if constexpr (STEM_NT_STORES) __builtin_nontemporal_store(f32x4{v.x, v.y, w.x, w.y}, (f32x4*)q);
+        else *(f32x4*)q = f32x4{v.x, v.y, w.x, w.y};
+    };
     // stores lo .. hi - 1 of the pending item.  set_tag: which accumulator set holds it (RI2);
     // scaled_tag: a strip_exponent run (RI2 scales at the store; the X / Y form scaled its copy)
     auto drain = [&](int lo, int hi, auto set_tag, auto scaled_tag) __attribute__((always_inline)) {
         constexpr int SET = decltype(set_tag)::value < NSET ? decltype(set_tag)::value : 0;
 #pragma unroll
         for (int i = lo; i < hi; ++i) {
-            if constexpr (RI2) {
+            if constexpr (P16) {
+                store4(pdst + 2 * out_t(i), pv[i], pw[i]);   // (the pending PAIR of items: rows of 2 x 32 columns)
+            } else if constexpr (RI2) {
                 // store i: accumulator i >> 3, register pair i & 7 (Re, Im adjacent)
                 float2 v;
                 v.x = cr[SET][i >> 3][2 * (i & 7)];
@@ -1212,8 +1229,12 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
     auto item2 = [&](int item, int64_t c_row, auto scaled_tag, auto drain_tag, auto defer_tag)
                      __attribute__((always_inline)) {
         constexpr bool DRAIN = decltype(drain_tag)::value;
-        if constexpr (DRAIN && (K2Q == 0 || BF3)) drain(0, NST, std::integral_constant<int, 0>{}, scaled_tag);   // (run-time trip count below: no slots to put them in)
+        // (P16, symmetric kernel: the first item's values stay pending in pv, this item's join them in pw)
+        if constexpr (DRAIN && !P16 && (K2Q == 0 || BF3)) drain(0, NST, std::integral_constant<int, 0>{}, scaled_tag);   // (run-time trip count below: no slots to put them in)
         const int cg = item / n_rt2, rt2 = item - cg * n_rt2;
+        // the lane's column of the result.  P16 (the wave's items wave, wave + SW share their row tile: n_rt2 divides SW):
+        // MFMA column l of the wave's item G is column 2 l + G of the 64 columns the wave owns (span wave / n_rt2)
+        const int col = PACK2 ? (l31 & 15) : (P16 ? 64 * ((item % SW) / n_rt2) + 2 * l31 + item / SW : cg * 32 + l31);
         f32x16 cx, cy;
         if constexpr (!XM2) {
 #pragma unroll
@@ -1226,14 +1247,14 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
         const float* bxp = b2x + cg * 32 * LDB2;
         const float* byp = PACK2 ? nullptr : b2y + cg * 32 * LDB2;
         // the result's addresses: scalar row base + lane part (LDS copy of the column table)
-        const int64_t c_col = oc_s[PACK2 ? (l31 & 15) : cg * 32 + l31];
+        const int64_t c_col = oc_s[col];
         const int nq = K2 >> 2;   // >= 4, even
         f32x4 af[2], bx[2], by[2];
         f32x16 cxm;   // XM2: the Im a Im b half of the real parts
         if constexpr (XM2) {
             // 16 k of one component per instruction: the lane halves take the blocks 2 c, 2 c + 1 of the Re
             // and of the Im plane; Xp += Re Re, Y += Re Im, Xm += Im Im, Y += Im Re -- no sign anywhere
-            const unsigned short* bR = Q2 + (cg * 32 + l31) * ROW2 + kk * 24;
+            const unsigned short* bR = Q2 + col * ROW2 + kk * 24;
             const unsigned short* bI = bR + N2 * ROW2;
             const float* aRf = mid + (rt2 * 32 + l31) * LD2 + kk * 8;
             // fragments of chunk c into set F: A' split here, B' from its planes
@@ -1367,7 +1388,8 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
         }
         {
             constexpr bool SC = decltype(scaled_tag)::value;
-            pdst = C + 2 * (c_row + out_lane + c_col);
+            constexpr bool SECOND = P16 && DRAIN;   // (the second item of a pair: the first one's address stands)
+            if constexpr (!SECOND) pdst = C + 2 * (c_row + out_lane + c_col);
             if (PACK2) {
                 // lane c < 16 holds Re of column c, lane c + 16 its Im: lanes below 16
                 // store row t, the others row t + 1 of each pair
@@ -1395,7 +1417,8 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
                     v.x = SC ? xr * alpha * alpha2 : xr;
                     v.y = SC ? cy[t] * alpha * alpha2 : cy[t];
                     if constexpr (BF3) h2_vmax = fmaxf(h2_vmax, fmaxf(fabsf(v.x), fabsf(v.y)));
-                    pv[t] = v;
+                    if constexpr (SECOND) pw[t] = v;
+                    else pv[t] = v;
                 }
             }
             if constexpr (!decltype(defer_tag)::value) drain(0, NST, std::integral_constant<int, 0>{}, scaled_tag);
@@ -1446,9 +1469,10 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
                 cy = AR::mfma(A_.ai[ta], B_.br[tb], cy);
             }
         };
-        // the accumulators become the item's pending stores
-        auto emit = [&](int cg) __attribute__((always_inline)) {
-            pdst = C + 2 * (c_row + out_lane + oc_s[cg * 32 + l31]);
+        // the accumulators become the item's pending stores (col: the lane's column of the result; P16, second group: its
+        // values join the first group's, one column to their right -- the pair goes out as one 16-byte store)
+        auto emit = [&](int col, auto second_tag) __attribute__((always_inline)) {
+            if constexpr (!decltype(second_tag)::value) pdst = C + 2 * (c_row + out_lane + oc_s[col]);
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
                 float2 v;
@@ -1456,14 +1480,19 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
                 v.x = SC ? xr * alpha * alpha2 : xr;
                 v.y = SC ? cy[t] * alpha * alpha2 : cy[t];
                 h2_vmax = fmaxf(h2_vmax, fmaxf(fabsf(v.x), fabsf(v.y)));
-                pv[t] = v;
+                if constexpr (decltype(second_tag)::value) pw[t] = v;
+                else pv[t] = v;
             }
         };
         static_for<0, 2>([&](auto gi) __attribute__((always_inline)) {
             constexpr int G = decltype(gi)::value;
             const int cg = cg0 + G * cgs;
-            const unsigned short* bR = Q2 + (cg * 32 + l31) * ROW2 + kk * 24;
-            if constexpr (G == 1) drain(0, NST, std::integral_constant<int, 0>{}, scaled_tag);   // the first item's stores
+            // P16: MFMA column l of group G is column 2 l + G of the 64 columns the consumer owns (span cg0 < cgs), not
+            // 32 (cg0 + G cgs) + l -- which row of B2's planes the lane reads, and which column it stores; the products
+            // an accumulator sees and their order do not change
+            const int col = P16 ? 64 * cg0 + 2 * l31 + G : cg * 32 + l31;
+            const unsigned short* bR = Q2 + col * ROW2 + kk * 24;
+            if constexpr (G == 1 && !P16) drain(0, NST, std::integral_constant<int, 0>{}, scaled_tag);   // the first item's stores
             if constexpr (G == 0) load_a(AK[0], 0);
             load_b(BF[0], bR, 0);
             static_for<0, NC>([&](auto ci) __attribute__((always_inline)) {
@@ -1474,7 +1503,7 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
                 }
                 mul(AK[CH], BF[CH & 1], CH == 0);
             });
-            emit(cg);
+            emit(col, std::integral_constant<bool, (P16 && G == 1)>{});
         });
     };
     // three-step tile: work item i of the middle stage -- (32 rows of the first intermediate) x BM's
@@ -1628,9 +1657,10 @@ __device__ __forceinline__ void stem2_body(const StemArgs& p) {
             const int64_t c_tile = tile_c(gc);
             int64_t c_rows[IT2];
             if constexpr (IT2 == 2 && XM2) {
-                if (n_rt2 <= PW) {   // (uniform: the wave's two items are one row tile's)
+                // (P16: the host launches this kernel for nothing else -- four row tiles, K2 = 64: stem_pair16_shape)
+                if (P16 || n_rt2 <= PW) {   // (uniform: the wave's two items are one row tile's)
                     const int nc = K2 >> 4;
-                    if (nc == 4) {
+                    if (P16 || nc == 4) {
                         item2k(std::integral_constant<int, 4>{}, wave1, item_row(wave1, c_tile), scaled_tag);
                         return;
                     }
@@ -1833,6 +1863,27 @@ template <bool PACK1, bool PACK2, int RT1_, int CS1, int NCH, int IT2_, bool BR1
 __global__ __launch_bounds__(SW * 64, 1) void stem2h_kernel(StemArgs p) {
     stem2_body<Fp16x2, PACK1, PACK2, RT1_, CS1, NCH, IT2_, BR1, K2Q, VEC, BF3, RI2, ONE, ITM, PACKM, XM, LM, WS>(p);
 }
+// The same kernels with PAIRED STORES (P16): a wave whose two items of step 2 are the two 32-column groups of ONE row tile
+// deals the result's columns to them alternately, so that a lane ends up with two ADJACENT elements of each of its 16
+// rows and writes them as one 16-byte store -- 16 store instructions of two complete 512-byte rows each where the kernels
+// above issue 32 of two 256-byte pieces.  Same products in the same order: bit-identical results.  Two families: the
+// consumers of the specialised-wave kernels (item2k, four chunks), and the symmetric kernels with two items per wave
+// (item2: the first item's values stay pending across the second one's multiplication; the pair goes out where the second
+// item's stores went, between the products of the next tile's first task).  Launched where the result's tables allow it
+// (stem_pair16_ok, ctg_runtime.hip) and the shape is one of the two (stem_pair16_shape below); symbols of their own, so a
+// trace tells the forms apart, with the 17 arguments of the kernel they stand in for (stem_kernel_name reports that one).
+template <bool PACK1, bool PACK2, int RT1_, int CS1, int NCH, int IT2_, bool BR1 = false, int K2Q = 0, bool VEC = false,
+          bool BF3 = false, bool RI2 = false, bool ONE = false, int ITM = 0, bool PACKM = false, bool XM = false,
+          bool LM = false, bool WS = false>
+__global__ __launch_bounds__(SW * 64, 1) void stem2_kernel_p16(StemArgs p) {
+    stem2_body<Bf16x3, PACK1, PACK2, RT1_, CS1, NCH, IT2_, BR1, K2Q, VEC, BF3, RI2, ONE, ITM, PACKM, XM, LM, WS, true>(p);
+}
+template <bool PACK1, bool PACK2, int RT1_, int CS1, int NCH, int IT2_, bool BR1 = false, int K2Q = 0, bool VEC = false,
+          bool BF3 = false, bool RI2 = false, bool ONE = false, int ITM = 0, bool PACKM = false, bool XM = false,
+          bool LM = false, bool WS = false>
+__global__ __launch_bounds__(SW * 64, 1) void stem2h_kernel_p16(StemArgs p) {
+    stem2_body<Fp16x2, PACK1, PACK2, RT1_, CS1, NCH, IT2_, BR1, K2Q, VEC, BF3, RI2, ONE, ITM, PACKM, XM, LM, WS, true>(p);
+}
 
 #ifdef CTG_STEM_TIMELINE
 // (experiment build only; behind ctg_debug_stem_timeline[_h2]) the stamps of the last launch: 8 x CTG_TL_TILES x 6 words
@@ -1871,6 +1922,11 @@ static auto stem_kernel() {
     if constexpr (AR::fp16) return stem2h_kernel<A...>;
     else return stem2_kernel<A...>;
 }
+template <class AR, auto... A>
+static auto stem_kernel_p16() {
+    if constexpr (AR::fp16) return stem2h_kernel_p16<A...>;
+    else return stem2_kernel_p16<A...>;
+}
 
 static size_t stem2_lds_bytes(const StemArgs& p) {
     const size_t b1 = (size_t)(p.N1 == 16 ? 3 : 2) * p.N1 * (p.K1 + 4);
@@ -1895,13 +1951,49 @@ static size_t stem2_lds_bytes_ri2(const StemArgs& p, bool b2_in_regs) {
     return 4 * (b1 + (b2_in_regs ? (mid > b2 ? mid : b2) : b2 + mid)) + 8 * (size_t)p.N2;
 }
 
+// Paired stores take a step whose tables allow them (StemArgs::pair16: the runtime's verdict on the step's own tables,
+// stem_pair16_ok) and whose waves hold both column groups of a row tile.  ws: a specialised-wave kernel with one item per
+// wave of the symmetric form -- its consumers run item2k: four row tiles of 64 columns, K2 = 64 (what the 8192 elements of
+// such a tile leave); else a symmetric kernel with two items per wave -- items wave and wave + SW share a row tile when the
+// row tiles divide the waves: 64 columns on eight row tiles, 128 on four.  Anything else keeps the 8-byte stores.
+// CTG_STEM_NO_PAIR16=1 (a diagnostic switch like CTG_STEM_FORM, read per launch; the tests compare the two forms with
+// it) keeps every step on them.
+static bool stem_pair16_shape(const StemArgs& p, bool ws) {
+    if (!p.pair16 || p.one || p.tri || env_on("CTG_STEM_NO_PAIR16")) return false;
+    const int n_rt2 = p.rows2 >> 5;
+    if (p.N2 != 32 * p.ng2 || n_rt2 < 1) return false;
+    if (ws) return n_rt2 == SW / 2 && p.ng2 == 2 && p.K2 == 64;
+    return n_rt2 <= SW && SW % n_rt2 == 0 && n_rt2 * p.ng2 == 2 * SW;
+}
+// The symmetric family is an EXPERIMENT BUILD (tools/build_variants.py pair16sym=-DCTG_STEM_PAIR16_SYM): holding the first
+// item's 16 values across the second item's multiplication costs registers these kernels do not have -- the two bf16 x 3
+// first-pair kernels of the headline spill 94 and 97 registers instead of 82 and 85, the fp16 x 2 kernel of the same
+// geometry 36 where it spilled none -- and the per-step table shows no gain (profiles/stem_paired_stores.txt section 8).
+#ifdef CTG_STEM_PAIR16_SYM
+constexpr bool STEM_PAIR16_SYM = true;
+#else
+constexpr bool STEM_PAIR16_SYM = false;
+#endif
+// what the last launch_stem of this object took: 1 paired stores, 0 the 8-byte form (the runtime keeps it per step:
+// ctg_exec_step_paired_stores reports what RAN, not a prediction)
+static int stem_last_paired = 0;
+
 template <class AR, bool PACK1, bool PACK2, int RT1, int CS1, int NCH, int IT2, bool BR1 = false, int K2Q = 0, bool VEC = false,
           bool BF3 = false, bool RI2 = false, bool XM = false, bool WS = false>
 static hipError_t launch_stem2_t(const StemArgs& p, hipStream_t stream) {
     auto kern = stem_kernel<AR, PACK1, PACK2, RT1, CS1, NCH, IT2, BR1, K2Q, VEC, BF3, RI2, false, 0, false, XM, false, WS>();
-    static unsigned long long ready = 0;   // (bit per device)
+    static unsigned long long ready = 0, ready16 = 0;   // (bit per device)
+    bool paired = false;
+    // paired stores: the kernels whose waves hold both column groups of a row tile
+    if constexpr (BF3 && XM && !PACK2 && NCH > 0 && ((AR::fp16 && WS && IT2 == 1) || (STEM_PAIR16_SYM && !WS && IT2 == 2))) {
+        if (stem_pair16_shape(p, WS)) {
+            kern = stem_kernel_p16<AR, PACK1, PACK2, RT1, CS1, NCH, IT2, BR1, K2Q, VEC, BF3, RI2, false, 0, false, XM, false, WS>();
+            paired = true;
+        }
+    }
+    stem_last_paired = paired ? 1 : 0;
     {
-        const hipError_t e = lds_opt_in((const void*)kern, 160 * 1024, &ready);
+        const hipError_t e = lds_opt_in((const void*)kern, 160 * 1024, paired ? &ready16 : &ready);
         if (e != hipSuccess) return e;
     }
 #ifdef CTG_STEM_TIMELINE

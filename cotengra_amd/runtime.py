@@ -42,6 +42,9 @@ SYMBOLS = (
     "ctg_exec_launch_count",
     "ctg_exec_profile_slice",
     "ctg_exec_step_kernel",
+    "ctg_exec_step_paired_stores",
+    "ctg_exec_step_stem_max",
+    "ctg_plan_stem_pair16",
     "ctg_exec_sync",
     "ctg_exec_result_ptr",
     "ctg_exec_result_stats",
@@ -157,6 +160,9 @@ def load():
         "ctg_exec_launch_count": [vp, i64p, i64p],
         "ctg_exec_profile_slice": [vp, C.c_int64, C.POINTER(C.c_float)],
         "ctg_exec_step_kernel": [vp, C.c_int64, C.c_char_p, C.c_int64],
+        "ctg_exec_step_paired_stores": [vp, C.c_int64, C.POINTER(C.c_int)],
+        "ctg_exec_step_stem_max": [vp, C.c_int64, C.c_int64, C.POINTER(C.c_float)],
+        "ctg_plan_stem_pair16": [vp, C.c_int64, C.POINTER(C.c_int)],
         "ctg_exec_sync": [vp],
         "ctg_exec_result_ptr": [vp, C.POINTER(vp)],
         "ctg_exec_result_stats": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), i64p],
@@ -298,6 +304,17 @@ class DevicePlan:
         n = C.c_int64()
         _check(load().ctg_plan_nslices(self.handle, C.byref(n)))
         return n.value
+
+    def stem_pair16(self):
+        """Per plan step: is it a stem pair whose result's tables allow 16-byte stores of two adjacent columns
+        (``ctg_plan_stem_pair16``)?  No device needed."""
+        fn = load().ctg_plan_stem_pair16
+        out = []
+        for s in range(len(self.plan.steps)):
+            v = C.c_int()
+            _check(fn(self.handle, s, C.byref(v)))
+            out.append(bool(v.value))
+        return out
 
     def share_units(self, rank=0, world=1):
         """``(units, slices per unit)`` of ``rank``'s share (``ctg_plan_share_units``): whole slice
@@ -456,6 +473,23 @@ class Executor:
             _check(load().ctg_exec_step_kernel(self.handle, s, buf, 160))
             names.append(buf.value.decode())
         return names
+
+    def step_paired_stores(self):
+        """Per plan step: did its last launch store two adjacent columns of a row as one 16-byte store
+        (``ctg_exec_step_paired_stores``: the kernel ``stem2h_kernel_p16`` of a trace)?"""
+        fn = load().ctg_exec_step_paired_stores
+        out = []
+        for s in range(len(self.plan.steps)):
+            v = C.c_int()
+            _check(fn(self.handle, s, C.byref(v)))
+            out.append(bool(v.value))
+        return out
+
+    def step_stem_max(self, step, z=0):
+        """The largest |component| the last launch of stem step ``step`` recorded of its result (``ctg_exec_step_stem_max``)."""
+        v = C.c_float()
+        _check(load().ctg_exec_step_stem_max(self.handle, int(step), int(z), C.byref(v)))
+        return float(v.value)
 
     def sync(self):
         _check(load().ctg_exec_sync(self.handle))

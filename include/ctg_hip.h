@@ -331,6 +331,26 @@ int ctg_exec_profile_slice(ctg_exec* exec, int64_t slice_id, float* ms);
  *   "pair_pick_rows_mfma_kernel<c64>"                        matrix-core form (row_lo >= 32, N >= 8, K >= 8)
  * Match by prefix. */
 int ctg_exec_step_kernel(ctg_exec* exec, int64_t step, char* buf, int64_t buflen);
+/* Added to ABI 10 WITHOUT a bump of CTG_ABI_VERSION: THREE new symbols, nothing else changes -- a plan, an executor and
+ * every existing call behave as before, which is the rule by which ABI 10 has grown (kernel codes 2 and 3, top-k,
+ * marginals, reduced density matrices); the binding binds them like every other symbol.
+ * A stem pair whose consumers hold both 32-column groups of a row tile stores two adjacent columns of a row as one
+ * 16-byte store where the step's own tables allow it: the paired columns exactly one element apart, every row, tile and
+ * slice offset and the result's place in its space even.  The kernel is then the symbol "stem2h_kernel_p16<...>" in a
+ * trace, with the template arguments of the "stem2h_kernel<...>" that ctg_exec_step_kernel goes on naming; results are
+ * bit for bit those of the 8-byte form.  *paired = 1 if the step's LAST launch took that form -- recorded by the
+ * launcher itself --, else 0 (a step that has not run, and any other kind of step, included).  CTG_STEM_NO_PAIR16=1 in
+ * the environment (a diagnostic switch, read per launch) keeps every step on 8-byte stores. */
+int ctg_exec_step_paired_stores(ctg_exec* exec, int64_t step, int* paired);
+/* The largest |real or imaginary part| that the last launch of stem step `step` recorded of what it stored, for slice `z`
+ * of the batch (0 for a step that slices share): what a consumer in the fp16 x 2 arithmetic scales its split with.
+ * Synchronises the stream.  CTG_E_INVALID for a step that is no stem step or whose last launch recorded nothing (fp32
+ * products, strip_exponent). */
+int ctg_exec_step_stem_max(ctg_exec* exec, int64_t step, int64_t z, float* mx);
+/* The verdict on the tables alone, of a plan in host memory: *ok = 1 if step `step` is
+ * a stem pair whose result's tables meet the condition above, else 0.  Which kernels then use it is the launch's
+ * business (shape, arithmetic and form of the step: ctg_exec_step_paired_stores). */
+int ctg_plan_stem_pair16(ctg_plan* plan, int64_t step, int* ok);
 
 int ctg_exec_sync(ctg_exec* exec);
 /* device address of the result tensor (result_elems elements, row-major in

@@ -39,8 +39,9 @@ def step_kernel_name(rocprof_name):
     m = re.match(r"pair_rowwise_kernel<(\d+), (true|false)>", rocprof_name)
     if m:
         return f"pair_rowwise_kernel<{m.group(1)},{m.group(2)}>"
-    m = re.match(r"(stem2h?_kernel)<([^>]*)>", rocprof_name)
-    if m:   # (template arguments spelled as csrc/ctg_stem.hip: stem2_kernel_name spells them; stem2h: fp16 x 2)
+    m = re.match(r"(stem2h?_kernel(?:_p16)?)<([^>]*)>", rocprof_name)
+    if m:   # (template arguments spelled as csrc/ctg_stem.hip: stem2_kernel_name spells them; stem2h: fp16 x 2;
+            # _p16: the launches of that instantiation with 16-byte stores -- an entry of their own, which no step name matches)
         return "%s<%s>" % (m.group(1), m.group(2).replace(" ", ""))
     m = re.match(r"pair_skinny_kernel<(\d+), (\d+)>", rocprof_name)
     if m:

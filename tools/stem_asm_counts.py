@@ -34,6 +34,10 @@ HEADLINE = [
     ("h2", "false,false,1,4,4,0,false,0,false,true,false,true,0,false,true,false"),
     ("h2", "false,false,1,2,8,0,false,0,false,true,false,true,0,false,true,false"),
     ("h2", "false,false,1,1,8,0,false,0,false,true,false,true,0,false,true,false"),
+    # the paired-store forms of the three kernels above whose consumers hold a row tile's two column groups (stem2h_kernel_p16)
+    ("h2p", "false,false,1,1,2,1,true,0,false,true,false,false,0,false,true,false,true"),
+    ("h2p", "false,false,1,2,2,1,false,0,false,true,false,false,0,false,true,false,true"),
+    ("h2p", "false,false,1,1,4,1,false,0,false,true,false,false,0,false,true,false,true"),
     ("bf3", "false,false,1,1,2,2,true,0,false,true,false,false,0,false,true,false,false"),
     ("bf3", "false,false,1,1,1,2,true,0,false,true,false,false,0,false,true,false,false"),
     ("bf3", "false,true,1,1,2,2,true,0,false,true,false,false,0,false,true,false,false"),
@@ -42,10 +46,11 @@ HEADLINE = [
 
 def compile_one(job):
     csrc, tmp, i, (ar, targs) = job
-    src = "ctg_stem_h2.hip" if ar == "h2" else "ctg_stem.hip"
+    src = "ctg_stem_h2.hip" if ar in ("h2", "h2p") else "ctg_stem.hip"
     out = os.path.join(tmp, f"k{i}.s")
     subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17",
-                    "--cuda-device-only", "-Wno-unused-command-line-argument", "-S", f"-DCTG_STEM_DEV_ONE={targs}", src, "-o", out],
+                    "--cuda-device-only", "-Wno-unused-command-line-argument", "-S", f"-DCTG_STEM_DEV_ONE={targs}", src, "-o", out]
+                   + (["-DCTG_STEM_DEV_P16"] if ar == "h2p" else []),
                    check=True, cwd=csrc)
     return open(out).read().split("\n")
 
@@ -123,7 +128,7 @@ def main():
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(min(16, len(HEADLINE))) as pool:
         texts = list(pool.map(compile_one, [(a.csrc, tmp, i, k) for i, k in enumerate(HEADLINE)]))
     for (ar, targs), L in zip(HEADLINE, texts):
-        lines.append(f"{'stem2h_kernel' if ar == 'h2' else 'stem2_kernel'}<{targs}>")
+        lines.append(f"{ {'h2': 'stem2h_kernel', 'h2p': 'stem2h_kernel_p16'}.get(ar, 'stem2_kernel') }<{targs}>")
         lines.append(f"   vgpr {note(L, 'vgpr_count')}  agpr {note(L, 'agpr_count')}  scratch {note(L, 'private_segment_fixed_size')} B"
                      f"  spilled vgprs {note(L, 'vgpr_spill_count')}  static lds {note(L, 'group_segment_fixed_size')} B")
         # (most MFMAs first: the order in which the compiler lays the roles out changes from build to build)
