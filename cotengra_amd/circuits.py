@@ -415,6 +415,82 @@ def reduced_density_matrix(n, gates, qubits, fixed=None, optimize="greedy", dtyp
     return res.rho / res.norm, res.norm
 
 
+def pauli_expectation(n, gates, paulis, fixed=None, coeffs=None, optimize="greedy", dtype="complex64", target_size=None):
+    """Expectation values of Pauli strings in the output state of the ``n``-qubit circuit ``gates``: energy terms of
+    a Hamiltonian, QAOA / MaxCut cost functions, stabiliser checks, correlators.  ``paulis``: a list of requests (or
+    one request), each a ``str`` of ``n`` letters over ``IXYZ`` (any case), qubit 0 first, or a dict ``{qubit:
+    letter}`` (qubits not named are I).  Every qubit not in ``fixed`` (a dict ``{qubit: 0 | 1}``, as for
+    :func:`reduced_density_matrix`) stays open, so the result tensor is the -- conditional, for a non-empty ``fixed``
+    -- state, and every ``<psi| P |psi>`` is taken on the device (``ContractionTree.contract_expectation``, DESIGN.md
+    section 16): strings that share their X / Y positions share one read of the state.  A fixed qubit must be I.
+
+    Returns ``(values, norm)``: ``values`` = ``<psi| P |psi> / norm`` per request (a float64 array; a 0-d float for
+    one request) and ``norm`` = ``sum |amplitude|^2`` of the open qubits (the probability of the fixed bits; 1 without
+    any).  With ``coeffs`` (one real per request) also the scalar ``sum_k coeffs[k] values[k]`` as a third item.
+    ``ValueError`` -- before any device work -- for a string of the wrong length, a letter outside ``IXYZ``, a qubit
+    outside the circuit, a fixed value other than 0 / 1, a letter other than I on a fixed qubit, ``coeffs`` of
+    another length than ``paulis`` and more than 4096 requests; and for a state of norm zero."""
+    from .interface import array_contract_tree
+
+    n = int(n)
+    fixed = {int(q): int(b) for q, b in (fixed or {}).items()}
+    for q, b in fixed.items():
+        if q < 0 or q >= n:
+            raise ValueError(f"fixed: qubit {q} outside the {n} qubits.")
+        if b not in (0, 1):
+            raise ValueError(f"fixed: qubit {q} is projected onto {b}; 0 or 1 is expected.")
+    several = not isinstance(paulis, (str, dict))
+    if several and not isinstance(paulis, (list, tuple)):
+        raise ValueError(f"pauli_expectation: paulis = {paulis!r}; a string, a dict or a list of those is expected.")
+    reqs = list(paulis) if several else [paulis]
+    if len(reqs) > 4096:
+        raise ValueError(f"pauli_expectation: {len(reqs)} requests; at most 4096 are taken by one call.")
+    letters = []
+    for req in reqs:
+        if isinstance(req, str):
+            if len(req) != n:
+                raise ValueError(f"pauli_expectation: {req!r} is not a string of {n} letters.")
+            named = dict(enumerate(req))
+        elif isinstance(req, dict):
+            named = {}
+            for q, c in req.items():
+                if isinstance(q, bool) or int(q) != q or not 0 <= int(q) < n:
+                    raise ValueError(f"pauli_expectation: qubit {q!r} outside the {n} qubits.")
+                named[int(q)] = c
+        else:
+            raise ValueError(f"pauli_expectation: the request {req!r} is neither a string nor a dict {{qubit: letter}}.")
+        row = {}
+        for q, c in named.items():
+            if not isinstance(c, str) or c.upper() not in ("I", "X", "Y", "Z"):
+                raise ValueError(f"pauli_expectation: {c!r} is none of the letters I, X, Y, Z.")
+            if c.upper() != "I":
+                if q in fixed:
+                    raise ValueError(f"pauli_expectation: qubit {q} is fixed and carries {c!r}; a fixed qubit must be I.")
+                row[q] = c.upper()
+        letters.append(row)
+    if coeffs is not None:
+        coeffs = np.asarray(coeffs, dtype=np.float64).reshape(-1)
+        if coeffs.size != len(reqs):
+            raise ValueError(f"pauli_expectation: {coeffs.size} coefficients for {len(reqs)} requests.")
+    template = "".join(str(fixed[q]) if q in fixed else "?" for q in range(n))
+    open_qubits = [q for q in range(n) if q not in fixed]
+    inputs, output, size_dict, arrays = circuit_to_network(n, gates, template, simplify=True, dtype=dtype)
+    tree = array_contract_tree(inputs, output, size_dict, optimize=optimize)
+    if [tuple(t) for t in tree.inputs] != [tuple(t) for t in inputs] or tuple(tree.output) != tuple(output):
+        raise ValueError("optimize: the tree is not over this circuit's network.")
+    if target_size is not None:
+        tree = tree.slice(target_size=target_size)
+    label = dict(zip(open_qubits, output))   # (one output index per open qubit, in qubit order)
+    res = tree.contract_expectation(arrays, [{label[q]: c for q, c in row.items()} for row in letters])
+    if not res.norm > 0:
+        raise ValueError("pauli_expectation: the state has norm zero.")
+    values = np.asarray(res.values, dtype=np.float64) / res.norm
+    out = (values if several else np.float64(values[0]), res.norm)
+    if coeffs is not None:
+        out += (float(np.dot(coeffs, values)),)
+    return out
+
+
 def _spectrum(rho):
     """Eigenvalues of the trace-normalised Hermitian matrix ``rho``, those below 0 from rounding clipped."""
     rho = np.asarray(rho)

@@ -327,6 +327,81 @@ def pick_requests(tree, coords=None, indices=None):
     return req
 
 
+_PAULI_CODE = {"I": 0, "X": 1, "Y": 2, "Z": 3}
+
+
+def pauli_requests(tree, paulis):
+    """``paulis`` of ``HipContractor.expectation`` as ``(several?, ops)`` with ``ops`` a uint8 array of shape
+    ``(m, len(tree.output))`` over ``tree.gathered_shape()``: 0, 1, 2, 3 = I, X, Y, Z per output index -- host only.
+    A request is a ``str`` of ``len(tree.output)`` letters over ``IXYZ`` (any case), one per output index in
+    ``tree.output`` order; a mapping ``{label: letter}``; or a sequence of ``(label, letter)`` pairs; labels not named
+    are I.  ``paulis`` is one request or a list of requests.  ``ValueError`` for an unknown or repeated label, a letter
+    outside ``IXYZ``, a string of the wrong length, a letter other than I on an output index whose extent is not 2 and
+    more than ``Executor.PAULI_MAX_STRINGS`` requests."""
+    import collections.abc as cabc
+
+    output = list(tree.output)
+    shape = tuple(int(d) for d in tree.gathered_shape())
+    rank = len(output)
+
+    def is_pair(p):
+        return isinstance(p, (tuple, list)) and len(p) == 2 and isinstance(p[1], str)
+
+    def code(letter):
+        if not isinstance(letter, str) or letter.upper() not in _PAULI_CODE:
+            raise ValueError(f"paulis: {letter!r} is none of the letters I, X, Y, Z.")
+        return _PAULI_CODE[letter.upper()]
+
+    if isinstance(paulis, (str, cabc.Mapping)):
+        several, reqs = False, [paulis]
+    elif isinstance(paulis, (list, tuple)):
+        if len(paulis) and all(is_pair(p) for p in paulis):
+            several, reqs = False, [paulis]
+        else:
+            several, reqs = True, list(paulis)
+    else:
+        raise ValueError(f"paulis = {paulis!r}: give a string over IXYZ, a mapping {{label: letter}}, a sequence of "
+                         "(label, letter) pairs, or a list of such requests.")
+    if len(reqs) > runtime.Executor.PAULI_MAX_STRINGS:
+        raise ValueError(f"paulis: {len(reqs)} requests; at most {runtime.Executor.PAULI_MAX_STRINGS} are taken by one call.")
+    ops = np.zeros((len(reqs), rank), dtype=np.uint8)
+    for r, req in enumerate(reqs):
+        if isinstance(req, str):
+            if len(req) != rank:
+                raise ValueError(f"paulis: {req!r} has {len(req)} letters; one per output index {output} is expected.")
+            pairs = list(zip(output, req))
+        elif isinstance(req, cabc.Mapping):
+            pairs = list(req.items())
+        elif isinstance(req, (list, tuple)) and all(is_pair(p) for p in req):
+            pairs = [tuple(p) for p in req]
+        else:
+            raise ValueError(f"paulis: the request {req!r} is no string, mapping or sequence of (label, letter) pairs.")
+        seen = set()
+        for ix, letter in pairs:
+            if ix not in output:
+                raise ValueError(f"paulis: {ix!r} is not an output index of the tree (output: {output}).")
+            if ix in seen:
+                raise ValueError(f"paulis: the label {ix!r} is named twice in one request.")
+            seen.add(ix)
+            a = output.index(ix)
+            c = code(letter)
+            if c and shape[a] != 2:
+                raise ValueError(f"paulis: {letter!r} on output index {ix!r} of extent {shape[a]}; only an index of "
+                                 "extent 2 carries X, Y or Z.")
+            ops[r, a] = c
+    return several, ops
+
+
+class ExpectationResult(collections.namedtuple("ExpectationResult", "values norm exponent")):
+    """What ``HipContractor.expectation`` returns: ``values`` the float64 array of ``<x| P |x> = sum over j of
+    conj(x[j]) (P x)[j]`` per requested Pauli string, in the caller's order and NOT normalised (a 0-d float for a
+    single request); ``norm`` = ``sum |x|^2`` of the whole result, the value of the all-identity string up to
+    rounding; the base-10 ``exponent`` taken out under ``strip_exponent`` (0.0 otherwise: true values are ``values
+    10^(2 exponent)``)."""
+
+    __slots__ = ()
+
+
 class HipContractor:
     """Callable performing the contraction of ``tree`` on an MI355X.
 
@@ -415,7 +490,8 @@ class HipContractor:
         # be multi-threaded (presets.py:77-88): upload -> run -> fetch is one critical section.
         self._lock = threading.RLock()
         # (executor state, strip_exponent) of the call made last if it left the whole contraction in the result
-        # tensor (__call__, sample, topk, marginal, rdm), None after anything else: what reuse=True reads (under _lock)
+        # tensor (__call__, sample, topk, marginal, rdm, expectation), None after anything else: what reuse=True reads
+        # (under _lock)
         self._reusable = None
 
     # ------------------------------------------------------------------ #
@@ -890,7 +966,7 @@ class HipContractor:
         the result dtype (a torch tensor for ROCm torch inputs); with ``strip_exponent`` ``(mantissa,
         exponent)`` as a call does.  ``M = 0``: an empty array, the device is not touched.  ``ValueError`` --
         before the device is touched -- for what :func:`pick_requests` refuses.  The result tensor of this
-        contractor is not touched, but ``reuse=True`` of :meth:`topk` / :meth:`marginal` / :meth:`rdm` refuses to read it after
+        contractor is not touched, but ``reuse=True`` of :meth:`topk` / :meth:`marginal` / :meth:`rdm` / :meth:`expectation` refuses to read it after
         a pick.  Not differentiable.
 
         ``chain`` (``True``, or an ``int``: at most that many levels below the root): the requests are carried
@@ -916,7 +992,8 @@ class HipContractor:
             fn = self._pick_contractor(req, chain)
             return fn._contract(arrays, False, check_zero, strip_exponent)
 
-    # ---- top-k, marginals and reduced density matrices of the result on the device -------- #
+    # ---- top-k, marginals, reduced density matrices and Pauli expectation values of the result on the device (DESIGN
+    # 12, 15, 16) -------- #
 
     def _reduce_state(self, arrays, strip_exponent, check_zero, reuse):
         """Under the lock: the executor state whose result tensor holds the whole contraction, and whether it was
@@ -946,7 +1023,7 @@ class HipContractor:
         (``ctg_exec_result_topk``).  Returns a :class:`TopKResult`.  With
         ``strip_exponent`` the amplitudes, ``p``, ``norm`` and ``sum_p2`` are the mantissa's.  ``reuse=True``
         (no arrays): read the result tensor left by the call made directly before on this contractor
-        (``__call__``, ``sample``, ``topk``, ``marginal`` or ``rdm``; its ``strip_exponent`` applies) instead of
+        (``__call__``, ``sample``, ``topk``, ``marginal``, ``rdm`` or ``expectation``; its ``strip_exponent`` applies) instead of
         contracting again; ``RuntimeError`` when there is none or another call came between.  ``ValueError`` for
         ``k < 1`` or above the number of elements or 2^20, and when the result holds a NaN or inf.  An all-zero
         result is no error.  Not differentiable."""
@@ -1020,6 +1097,32 @@ class HipContractor:
             norm = ex.sample_info()[0]
             exponent = ex.get_exponent()[0] if strip else 0.0
         return RdmResult(rho=rhos if several else rhos[0], dims=dims if several else dims[0], norm=norm, exponent=exponent)
+
+    def expectation(self, *arrays, paulis, strip_exponent=False, check_zero=False, reuse=False):
+        """Contract (all slices, as a call does) and return ``<x| P |x> = sum over j of conj(x[j]) (P x)[j]`` of the
+        result for the Pauli strings ``paulis`` over the output indices -- every product and sum in double with a
+        fixed order, on the device; the result tensor is never copied to the host (``ctg_exec_result_pauli``,
+        DESIGN.md section 16).  ``paulis``: one request or a list of requests (:func:`pauli_requests`): a ``str`` of
+        one letter over ``IXYZ`` per output index in ``tree.output`` order, a mapping ``{label: letter}`` or a
+        sequence of ``(label, letter)`` pairs; labels not named are I.  Strings that share their X / Y positions
+        share one read of the tensor (all Z-type terms of an Ising cost function, say); the bits of a value do not
+        depend on the other strings of the call.  Values are NOT normalised: divide by ``norm``.  Returns an
+        :class:`ExpectationResult`.  ``ValueError`` -- before the device is touched -- for what
+        :func:`pauli_requests` refuses.  ``reuse=True``: as for :meth:`topk`.  Not differentiable."""
+        several, ops = pauli_requests(self.tree, paulis)
+        if reuse and arrays:
+            raise ValueError("reuse=True reads the result of the call before: give no arrays.")
+        shape = tuple(self.tree.gathered_shape())
+        with self._lock:
+            st, strip = self._reduce_state(arrays, strip_exponent, check_zero, reuse)
+            ex = st["exec"]
+            values = ex.pauli_result(shape, ops)
+            if len(values):
+                norm = ex.sample_info()[0]   # (of the statistics passes the call just ran)
+            else:
+                norm = ex.result_stats()[0]
+            exponent = ex.get_exponent()[0] if strip else 0.0
+        return ExpectationResult(values=values if several else np.float64(values[0]), norm=norm, exponent=exponent)
 
     def profile(self, arrays, slice_id=0):
         """Per-step milliseconds for one slice (see ``Plan.describe_steps``)."""

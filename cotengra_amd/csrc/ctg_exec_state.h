@@ -215,7 +215,7 @@ struct MarginalPlan {
 // CTG_OK, or CTG_E_INVALID with *why set
 __attribute__((visibility("hidden"))) int marginal_plan(int64_t rank, const int64_t* extents, const int32_t* keep,
                                                         int64_t result_elems, MarginalPlan* out, const char** why);
-// the executor's scratch of ctg_reduce.hip / ctg_rdm.hip (d_reduce), at least `want` bytes; the stream must be idle
+// the executor's scratch of ctg_reduce.hip / ctg_rdm.hip / ctg_pauli.hip (d_reduce), at least `want` bytes; the stream must be idle
 // (the statistics call synchronised it).  CTG_OK, CTG_E_NOMEM or CTG_E_HIP with the error set.
 __attribute__((visibility("hidden"))) int reduce_reserve(ctg_exec* e, int64_t want);
 }

@@ -251,6 +251,16 @@ class ContractExpression:
         self._after_reduce()
         return out
 
+    def expectation(self, *arrays, paulis, **kwargs):
+        """``expr(*arrays)`` followed by the expectation values of the Pauli strings ``paulis`` over the output
+        indices on the device (``HipContractor.expectation``); the expression's own ``strip_exponent`` /
+        ``check_zero`` unless given."""
+        kwargs.setdefault("strip_exponent", self.fn.strip_exponent)
+        kwargs.setdefault("check_zero", self.fn.check_zero)
+        out = self.fn.expectation(*arrays, paulis=paulis, **kwargs)
+        self._after_reduce()
+        return out
+
     def device_bytes(self):
         """Device memory this expression's executors hold right now (``ctg_exec_device_bytes``:
         arena x slice batch, inputs, tables, result, scratch), read under the contractor's lock

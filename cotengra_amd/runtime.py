@@ -54,6 +54,7 @@ SYMBOLS = (
     "ctg_exec_result_topk",
     "ctg_exec_result_marginal",
     "ctg_exec_result_rdm",
+    "ctg_exec_result_pauli",
     "ctg_exec_download_result",
     "ctg_exec_download_arena",
     "ctg_exec_get_state",
@@ -173,6 +174,7 @@ def load():
         "ctg_exec_result_topk": [vp, C.c_int64, i64p, vp, C.POINTER(C.c_double)],
         "ctg_exec_result_marginal": [vp, C.c_int64, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_double)],
         "ctg_exec_result_rdm": [vp, C.c_int64, i64p, C.POINTER(C.c_int32), vp],
+        "ctg_exec_result_pauli": [vp, C.c_int64, i64p, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_double)],
         "ctg_exec_download_result": [vp, vp],
         "ctg_exec_download_arena": [vp, C.c_int64, C.c_int64, vp],
         "ctg_exec_get_state": [vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_int)],
@@ -267,6 +269,85 @@ def rdm_variant(dtype, extents, keep):
     if n >= 4096 and all(v & (v - 1) == 0 for v in ext):
         return f"rdm_chunk_kernel<{t},{max(d, 16) // 16}>"
     return f"rdm_general_kernel<{t}>"
+
+
+_DTYPE_TAG = {"float32": "float", "float64": "double", "complex64": "c64", "complex128": "c128"}
+
+
+def _pauli_ops(extents, ops):
+    """``(extents as ints, n, ops as a C-contiguous uint8 (m, rank) array)`` of a Pauli request, validated as
+    ``ctg_exec_result_pauli`` validates it -- host only: ``ValueError`` for an extent below 1, a row of the wrong
+    length, a code above 3, a non-identity code on an axis whose extent is not 2 and more than
+    ``Executor.PAULI_MAX_STRINGS`` strings."""
+    ext = [int(v) for v in extents]
+    n = 1
+    for v in ext:
+        if v < 1:
+            raise ValueError(f"extent {v} is not positive.")
+        n *= v
+    raw = np.asarray(ops)
+    if raw.size and raw.dtype.kind not in "iub":
+        raise ValueError(f"pauli: codes of dtype {raw.dtype}; integers 0 .. 3 (I, X, Y, Z) are expected.")
+    if raw.size and (raw.min() < 0 or raw.max() > 3):
+        raise ValueError("pauli: a code is none of 0, 1, 2, 3 (I, X, Y, Z).")
+    if raw.ndim == 1 and raw.size == len(ext) and len(ext) > 0:
+        raw = raw.reshape(1, len(ext))
+    if raw.ndim != 2 or raw.shape[1] != len(ext):
+        raise ValueError(f"pauli: codes of shape {raw.shape}; (m, {len(ext)}) is expected, one column per axis.")
+    arr = np.ascontiguousarray(raw, dtype=np.uint8)
+    if arr.shape[0] > Executor.PAULI_MAX_STRINGS:
+        raise ValueError(f"pauli: {arr.shape[0]} strings; at most {Executor.PAULI_MAX_STRINGS} (CTG_PAULI_MAX_STRINGS) "
+                         "per call.")
+    for a, v in enumerate(ext):
+        if v != 2 and arr[:, a].any():
+            raise ValueError(f"pauli: a letter other than I on axis {a} of extent {v}; only an axis of extent 2 "
+                             "carries X, Y or Z.")
+    return ext, n, arr
+
+
+def _pauli_fast(ext, n):
+    return n >= 4096 and all(v & (v - 1) == 0 for v in ext)
+
+
+def pauli_masks(extents, ops):
+    """``[(xm, zm, ny), ...]`` per string of ``ops`` (``(m, rank)`` codes 0 .. 3 = I, X, Y, Z over a tensor of shape
+    ``extents``) as the power-of-two route of ``ctg_exec_result_pauli`` sees it: ``xm`` the flat-index bits of the X
+    and Y axes, ``zm`` those of the Z and Y axes, ``ny`` the number of Y.  The flat bit of an axis is log2 of its
+    row-major stride.  Host only; ``ValueError`` for what the call refuses and for an extent that is no power of
+    two."""
+    ext, n, arr = _pauli_ops(extents, ops)
+    if any(v & (v - 1) for v in ext):
+        raise ValueError(f"pauli_masks: the extents {tuple(ext)} are not all powers of two.")
+    stride, s = [0] * len(ext), 1
+    for a in range(len(ext) - 1, -1, -1):
+        stride[a] = s
+        s *= ext[a]
+    out = []
+    for row in arr.tolist():
+        xm = zm = ny = 0
+        for a, op in enumerate(row):
+            if op in (1, 2):
+                xm |= stride[a]
+            if op in (2, 3):
+                zm |= stride[a]
+            ny += op == 2
+        out.append((xm, zm, ny))
+    return out
+
+
+def pauli_variant(dtype, extents, ops):
+    """The kernel ``ctg_exec_result_pauli`` runs for a result of ``dtype`` and shape ``extents`` and the strings
+    ``ops`` -- a function of those alone (csrc/ctg_pauli.hip): ``"pauli_chunk_kernel<T>"`` on the power-of-two route
+    (every extent a power of two, at least 4096 elements), ``"pauli_general_kernel<T>"`` otherwise; ``T`` one of
+    ``float``, ``double``, ``c64``, ``c128``; ``"none"`` when every string is answered without a launch (no string,
+    or a real ``dtype`` and an odd number of Y in every string)."""
+    name = np.dtype(dtype).name
+    t = _DTYPE_TAG[name]
+    ext, n, arr = _pauli_ops(extents, ops)
+    odd = (arr == 2).sum(axis=1) % 2 == 1
+    if arr.shape[0] == 0 or (np.dtype(dtype).kind != "c" and bool(odd.all())):
+        return "none"
+    return f"pauli_chunk_kernel<{t}>" if _pauli_fast(ext, n) else f"pauli_general_kernel<{t}>"
 
 
 class DevicePlan:
@@ -597,6 +678,30 @@ class Executor:
     def rdm_variant(self, extents, keep):
         """The name of the kernel ``rdm_result(extents, keep)`` runs on this executor (:func:`rdm_variant`)."""
         return rdm_variant(self.plan.dtype, extents, keep)
+
+    # -- expectation values of Pauli strings over the result tensor (csrc/ctg_pauli.hip) -- #
+
+    PAULI_MAX_STRINGS = 4096   # CTG_PAULI_MAX_STRINGS
+
+    def pauli_result(self, extents, ops):
+        """``value(P) = sum over j of conj(x[j]) (P x)[j]`` of the result tensor for every Pauli string of ``ops``
+        (``ctg_exec_result_pauli``): ``extents`` is the shape of the result, ``ops`` an ``(m, rank)`` array of codes
+        0, 1, 2, 3 = I, X, Y, Z, one column per axis; an axis that is not I must have extent 2.  A float64 ``(m,)``
+        array, NOT normalised (the all-identity string gives ``sum p``); for a real plan a string with an odd number
+        of Y is exactly 0.0.  The bits of a value do not depend on the other strings of the call.  ``ValueError`` for
+        a wrong product of the extents, a code above 3, a letter other than I on an axis of another extent, more than
+        ``PAULI_MAX_STRINGS`` strings (nothing is launched) and for a result whose ``sum p`` is not finite."""
+        ext, n, arr = _pauli_ops(extents, ops)
+        e = np.ascontiguousarray(ext, dtype=np.int64).reshape(-1)
+        out = np.zeros(arr.shape[0], dtype=np.float64)
+        _check(load().ctg_exec_result_pauli(self.handle, e.size, _i64p(e), arr.shape[0],
+                                            arr.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                            out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def pauli_variant(self, extents, ops):
+        """The name of the kernel ``pauli_result(extents, ops)`` runs on this executor (:func:`pauli_variant`)."""
+        return pauli_variant(self.plan.dtype, extents, ops)
 
     # -- range audit (csrc/ctg_range.hip, cotengra_amd/rangeaudit.py) -- #
 

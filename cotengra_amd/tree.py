@@ -1102,6 +1102,15 @@ class ContractionTree:
 
         return _tree_contractor(self, order).rdm(*arrays, keep=keep, **kwargs)
 
+    def contract_expectation(self, arrays, paulis, order=None, **kwargs):
+        """:meth:`contract` followed by the expectation values ``<x| P |x>`` of the Pauli strings ``paulis`` over
+        the output indices (a string over ``IXYZ``, a mapping ``{label: letter}``, a sequence of ``(label, letter)``
+        pairs, or a list of such requests) on the device (``HipContractor.expectation``; ``kwargs``:
+        ``strip_exponent``, ``check_zero``, ``reuse``).  Not differentiable."""
+        from .contractor import _tree_contractor
+
+        return _tree_contractor(self, order).expectation(*arrays, paulis=paulis, **kwargs)
+
     def contract_audit(self, arrays, slices=(0,), order=None):
         """Range audit of the contraction on ``arrays`` (``HipContractor.audit``): the
         slices ``slices`` run step by step, one record per plan step with the exponent statistics of its

@@ -273,8 +273,8 @@ int ctg_exec_run_share(ctg_exec* exec, int64_t rank, int64_t world, int64_t unit
 /* ABI 4.  Device memory this executor holds right now: inputs space, arena x slice batch,
  * tables, the result if it owns it, the scratch buffer if the plan has a step that needs one
  * (allocated by ctg_exec_create), the scratch of ctg_exec_result_stats / ctg_exec_sample_result once they
- * have run (ABI 9), of ctg_exec_range_audit and of ctg_exec_result_topk / ctg_exec_result_marginal / ctg_exec_result_rdm
- * likewise (ABI 10).  What a cache of contractors -- the reference keeps them
+ * have run (ABI 9), of ctg_exec_range_audit and of ctg_exec_result_topk / ctg_exec_result_marginal / ctg_exec_result_rdm /
+ * ctg_exec_result_pauli likewise (ABI 10).  What a cache of contractors -- the reference keeps them
  * on the tree, core.py:3708-3722 -- has to count against its budget. */
 int ctg_exec_device_bytes(ctg_exec* exec, int64_t* bytes);
 /* ABI 5.  Is there a kernel instantiation for a three-step tile of this shape (stem steps fused
@@ -478,6 +478,43 @@ int ctg_exec_result_marginal(ctg_exec* exec, int64_t rank, const int64_t* extent
  * ctg_exec_reduce the root's result tensor holds the total and the call works there (untested). */
 #define CTG_RDM_MAX_DIM 64
 int ctg_exec_result_rdm(ctg_exec* exec, int64_t rank, const int64_t* extents, const int32_t* keep, void* out);
+/* Added to ABI 10 WITHOUT a bump of CTG_ABI_VERSION likewise (one new symbol; a binding that needs it looks it up):
+ * expectation values of Pauli strings over the axes of the result tensor on the device (csrc/ctg_pauli.hip, DESIGN.md
+ * section 16).  extents[rank] is the shape of the result (its product must equal result_elems); ops[m * rank],
+ * row-major, gives every axis of every string one of I, X, Y, Z as 0, 1, 2, 3 (Y = [[0, -i], [i, 0]]); an axis that
+ * is not I must have extent 2.  out[s], one double per string for every dtype, receives
+ *   value(P) = sum over j of conj(x[j]) (P x)[j],
+ * NOT normalised (the all-identity string gives sum p).  With xm the flat-index bits of the X and Y axes, zm those of
+ * the Z and Y axes, ny the number of Y and S = sum over j of (-1)^popcount(j & zm) conj(x[j ^ xm]) x[j]:
+ * value = (-1)^(ny/2) Re S for even ny, (-1)^((ny+1)/2) Im S for odd ny.  For real plans a string with odd ny is
+ * exactly 0.0 and is written without a launch.  The tensor is read as the calls above read it (whoever owns the
+ * memory, the mantissa under strip_exponent, after the stream's earlier work, after the statistics passes, which run
+ * first); the stream is synchronised.  CTG_E_NORM when sum p is not finite; an all-zero tensor gives zeros.
+ * CTG_E_INVALID -- checked on the host before anything is launched, the tensor untouched -- for a null exec, extents,
+ * ops or out, rank < 0, an extents product other than result_elems, m < 0 or m > CTG_PAULI_MAX_STRINGS, a code above 3
+ * and a non-identity code on an axis whose extent is not 2.  m = 0 succeeds and does nothing.
+ *   - Every product is formed in fp64 -- exact for float / complex64 plans, rounded once for double plans -- and every
+ *     sum is in fp64; no floating-point atomics.  |out[s] - exact| <= (t + 1) 2^-53 sum p with t = 2 result_elems
+ *     (complex) or result_elems (real) products.
+ *   - The bits of out[s] are a function of (dtype, extents, row s of ops, the tensor's bytes) alone: not of the other
+ *     strings of the call, their order, earlier calls in the same scratch, or the executor.  One accumulator per
+ *     string; grids and the dealing of chunks do not depend on how many strings share a pass.
+ * The strings of a call are grouped by xm (groups in order of first appearance, the caller's order inside) and a group
+ * runs in passes of at most 32 strings, each pass one read of the tensor: of every unordered pair {j, j ^ xm} one
+ * member is summed and the sum doubled, exactly, at the end (xm = 0: the term is |x[j]|^2, every j is summed).  Every
+ * extent a power of two and at least 4096 elements: "pauli_chunk_kernel<T>", T in float | double | c64 | c128 -- chunks
+ * of 4096 elements (chunk pairs (c, c ^ (xm >> 12)) where xm reaches past a chunk), the partner from an LDS copy, the
+ * signs from one 32-bit word per element and one per chunk, 32 fp64 accumulators per thread; a workgroup takes the
+ * units wg, wg + grid, ... in ascending order, grid = min(512, ceil(units / 3)); lanes and waves are added in a fixed
+ * order, the workgroups' partials in ascending order in groups of 32, then the groups.  Any other shape:
+ * "pauli_general_kernel<T>", a serial walk per (string, chunk of max(1024, ceil(result_elems / 1024)) flat indices),
+ * the chunks added in ascending order; not tuned.  Scratch: the buffer of the calls above (counted by
+ * ctg_exec_device_bytes, freed by ctg_exec_destroy): 8 m bytes of values and 648 bytes per pass, 128 KiB of partials,
+ * 4 KiB of group sums (2.8 MiB at most; general route: 32 bytes per string, 12 per non-identity letter, 8 per (string,
+ * chunk): 35 MiB at most).  Not differentiable.  No multi-rank entry: after ctg_exec_reduce the root's result tensor
+ * holds the total and the call works there (untested). */
+#define CTG_PAULI_MAX_STRINGS 4096
+int ctg_exec_result_pauli(ctg_exec* exec, int64_t rank, const int64_t* extents, int64_t m, const uint8_t* ops, double* out);
 /* debugging aid: copy `n` elements of the arena starting at element `offset`
  * to the host (synchronous) */
 int ctg_exec_download_arena(ctg_exec* exec, int64_t offset, int64_t n, void* host_out);
