@@ -415,6 +415,52 @@ def reduced_density_matrix(n, gates, qubits, fixed=None, optimize="greedy", dtyp
     return res.rho / res.norm, res.norm
 
 
+def _circuit_pauli_requests(who, n, paulis, fixed, coeffs):
+    """The validation ``pauli_expectation`` and ``energy_gradient`` share -- host only: ``(n, fixed, several?,
+    [{qubit: letter}, ...] without identities, coeffs as float64 or None)``."""
+    n = int(n)
+    fixed = {int(q): int(b) for q, b in (fixed or {}).items()}
+    for q, b in fixed.items():
+        if q < 0 or q >= n:
+            raise ValueError(f"fixed: qubit {q} outside the {n} qubits.")
+        if b not in (0, 1):
+            raise ValueError(f"fixed: qubit {q} is projected onto {b}; 0 or 1 is expected.")
+    several = not isinstance(paulis, (str, dict))
+    if several and not isinstance(paulis, (list, tuple)):
+        raise ValueError(f"{who}: paulis = {paulis!r}; a string, a dict or a list of those is expected.")
+    reqs = list(paulis) if several else [paulis]
+    if len(reqs) > 4096:
+        raise ValueError(f"{who}: {len(reqs)} requests; at most 4096 are taken by one call.")
+    letters = []
+    for req in reqs:
+        if isinstance(req, str):
+            if len(req) != n:
+                raise ValueError(f"{who}: {req!r} is not a string of {n} letters.")
+            named = dict(enumerate(req))
+        elif isinstance(req, dict):
+            named = {}
+            for q, c in req.items():
+                if isinstance(q, bool) or int(q) != q or not 0 <= int(q) < n:
+                    raise ValueError(f"{who}: qubit {q!r} outside the {n} qubits.")
+                named[int(q)] = c
+        else:
+            raise ValueError(f"{who}: the request {req!r} is neither a string nor a dict {{qubit: letter}}.")
+        row = {}
+        for q, c in named.items():
+            if not isinstance(c, str) or c.upper() not in ("I", "X", "Y", "Z"):
+                raise ValueError(f"{who}: {c!r} is none of the letters I, X, Y, Z.")
+            if c.upper() != "I":
+                if q in fixed:
+                    raise ValueError(f"{who}: qubit {q} is fixed and carries {c!r}; a fixed qubit must be I.")
+                row[q] = c.upper()
+        letters.append(row)
+    if coeffs is not None:
+        coeffs = np.asarray(coeffs, dtype=np.float64).reshape(-1)
+        if coeffs.size != len(reqs):
+            raise ValueError(f"{who}: {coeffs.size} coefficients for {len(reqs)} requests.")
+    return n, fixed, several, letters, coeffs
+
+
 def pauli_expectation(n, gates, paulis, fixed=None, coeffs=None, optimize="greedy", dtype="complex64", target_size=None):
     """Expectation values of Pauli strings in the output state of the ``n``-qubit circuit ``gates``: energy terms of
     a Hamiltonian, QAOA / MaxCut cost functions, stabiliser checks, correlators.  ``paulis``: a list of requests (or
@@ -432,46 +478,7 @@ def pauli_expectation(n, gates, paulis, fixed=None, coeffs=None, optimize="greed
     another length than ``paulis`` and more than 4096 requests; and for a state of norm zero."""
     from .interface import array_contract_tree
 
-    n = int(n)
-    fixed = {int(q): int(b) for q, b in (fixed or {}).items()}
-    for q, b in fixed.items():
-        if q < 0 or q >= n:
-            raise ValueError(f"fixed: qubit {q} outside the {n} qubits.")
-        if b not in (0, 1):
-            raise ValueError(f"fixed: qubit {q} is projected onto {b}; 0 or 1 is expected.")
-    several = not isinstance(paulis, (str, dict))
-    if several and not isinstance(paulis, (list, tuple)):
-        raise ValueError(f"pauli_expectation: paulis = {paulis!r}; a string, a dict or a list of those is expected.")
-    reqs = list(paulis) if several else [paulis]
-    if len(reqs) > 4096:
-        raise ValueError(f"pauli_expectation: {len(reqs)} requests; at most 4096 are taken by one call.")
-    letters = []
-    for req in reqs:
-        if isinstance(req, str):
-            if len(req) != n:
-                raise ValueError(f"pauli_expectation: {req!r} is not a string of {n} letters.")
-            named = dict(enumerate(req))
-        elif isinstance(req, dict):
-            named = {}
-            for q, c in req.items():
-                if isinstance(q, bool) or int(q) != q or not 0 <= int(q) < n:
-                    raise ValueError(f"pauli_expectation: qubit {q!r} outside the {n} qubits.")
-                named[int(q)] = c
-        else:
-            raise ValueError(f"pauli_expectation: the request {req!r} is neither a string nor a dict {{qubit: letter}}.")
-        row = {}
-        for q, c in named.items():
-            if not isinstance(c, str) or c.upper() not in ("I", "X", "Y", "Z"):
-                raise ValueError(f"pauli_expectation: {c!r} is none of the letters I, X, Y, Z.")
-            if c.upper() != "I":
-                if q in fixed:
-                    raise ValueError(f"pauli_expectation: qubit {q} is fixed and carries {c!r}; a fixed qubit must be I.")
-                row[q] = c.upper()
-        letters.append(row)
-    if coeffs is not None:
-        coeffs = np.asarray(coeffs, dtype=np.float64).reshape(-1)
-        if coeffs.size != len(reqs):
-            raise ValueError(f"pauli_expectation: {coeffs.size} coefficients for {len(reqs)} requests.")
+    n, fixed, several, letters, coeffs = _circuit_pauli_requests("pauli_expectation", n, paulis, fixed, coeffs)
     template = "".join(str(fixed[q]) if q in fixed else "?" for q in range(n))
     open_qubits = [q for q in range(n) if q not in fixed]
     inputs, output, size_dict, arrays = circuit_to_network(n, gates, template, simplify=True, dtype=dtype)
@@ -489,6 +496,66 @@ def pauli_expectation(n, gates, paulis, fixed=None, coeffs=None, optimize="greed
     if coeffs is not None:
         out += (float(np.dot(coeffs, values)),)
     return out
+
+
+def gate_derivatives(name, params=()):
+    """``[dU / d params[0], ...]`` of :func:`gate_matrix`, analytic: one matrix for ``rz``, two for ``fs``, none for a
+    gate without parameters."""
+    if name == "rz":
+        (theta,) = params
+        return [np.diag([-0.5j * np.exp(-0.5j * theta), 0.5j * np.exp(0.5j * theta)])]
+    if name == "fs":
+        theta, phi = params
+        c, sn = np.cos(theta), np.sin(theta)
+        d_theta = np.array([[0, 0, 0, 0], [0, -sn, -1j * c, 0], [0, -1j * c, -sn, 0], [0, 0, 0, 0]], dtype=complex)
+        d_phi = np.zeros((4, 4), dtype=complex)
+        d_phi[3, 3] = -1j * np.exp(-1j * phi)
+        return [d_theta, d_phi]
+    gate_matrix(name, params)   # (ValueError for an unknown gate)
+    return []
+
+
+def energy_gradient(n, gates, paulis, coeffs, fixed=None, optimize="greedy", dtype="complex64", target_size=None,
+                    normalize=True):
+    """Energy ``sum_k coeffs[k] <psi| P_k |psi>`` of the output state of the ``n``-qubit circuit ``gates`` and its
+    derivative by every gate parameter, in one step on the device: a VQE / QAOA iteration.  ``paulis``, ``fixed``:
+    as for :func:`pauli_expectation`; ``coeffs``: one real per request.  The network is built unsimplified, so leaf
+    ``n + k`` of the tree is gate ``k``; ``ContractionTree.contract_energy`` gives the energy
+    and its gradient by every gate tensor, and the chain rule with the analytic ``dU / d theta``
+    (:func:`gate_derivatives`) the derivative by every parameter.  ``normalize`` (default): the energy is divided by
+    ``norm`` = ``sum |amplitude|^2`` of the open qubits and that quotient is differentiated.
+
+    Returns ``(energy, norm, dparams)``: ``dparams[k]`` a float64 array with one entry per parameter of gate ``k``
+    (one for ``rz``, two for ``fs``, empty otherwise).  ``ValueError`` -- before any device work -- for what
+    :func:`pauli_expectation` refuses and for coefficients that are not finite; and for a state of norm zero under
+    ``normalize``."""
+    from .interface import array_contract_tree
+
+    if coeffs is None:
+        raise ValueError("energy_gradient: coeffs is None; one real coefficient per request is expected.")
+    n, fixed, several, letters, coeffs = _circuit_pauli_requests("energy_gradient", n, paulis, fixed, coeffs)
+    if not np.all(np.isfinite(coeffs)):
+        raise ValueError("energy_gradient: a coefficient is not finite.")
+    gates = list(gates)
+    derivs = [gate_derivatives(name, params) for name, _, params in gates]
+    template = "".join(str(fixed[q]) if q in fixed else "?" for q in range(n))
+    open_qubits = [q for q in range(n) if q not in fixed]
+    inputs, output, size_dict, arrays = circuit_to_network(n, gates, template, simplify=False, dtype=dtype)
+    tree = array_contract_tree(inputs, output, size_dict, optimize=optimize)
+    if [tuple(t) for t in tree.inputs] != [tuple(t) for t in inputs] or tuple(tree.output) != tuple(output):
+        raise ValueError("optimize: the tree is not over this circuit's network.")
+    if target_size is not None:
+        tree = tree.slice(target_size=target_size)
+    label = dict(zip(open_qubits, output))   # (one output index per open qubit, in qubit order)
+    wrt = [n + k for k, d in enumerate(derivs) if d]
+    res = tree.contract_energy(arrays, [{label[q]: c for q, c in row.items()} for row in letters], coeffs=coeffs,
+                               wrt=wrt, normalize=normalize)
+    dparams = []
+    for k, ds in enumerate(derivs):
+        g = None if not ds else np.asarray(res.grads[n + k], dtype=np.complex128).reshape(-1)
+        # dE = Re sum conj(dE / d Re U + i dE / d Im U) dU
+        dparams.append(np.array([float(np.real(np.vdot(g, d.reshape(-1)))) for d in ds], dtype=np.float64))
+    return float(res.energy), res.norm, dparams
 
 
 def _spectrum(rho):

@@ -219,6 +219,58 @@ def _autograd_function():
     return ContractFunction
 
 
+_EnergyFunction = None
+
+
+def _energy_function():
+    """The ``torch.autograd.Function`` of ``HipContractor.energy_autograd`` (built on first use).  The forward is
+    :meth:`HipContractor._energy_forward` -- the bits of the call without autograd -- and saves ``y``; the backward
+    takes the real ``grad_output`` and runs one VJP plan at the cotangent ``grad_output conj(2 y)``."""
+    global _EnergyFunction
+    if _EnergyFunction is not None:
+        return _EnergyFunction
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class EnergyFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fn, ops, coeffs, normalize, box, *arrays):
+            ctx.fn = fn
+            ctx.arrays = [x.detach() if _is_torch(x) else x for x in arrays]
+            energy, box["values"], box["norm"], ctx.y = fn._energy_forward(ctx.arrays, ops, coeffs, normalize)
+            return torch.tensor(energy, dtype=torch.float64, device=ctx.y.device)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_output):
+            wrt = tuple(i for i, need in enumerate(ctx.needs_input_grad[5:]) if need)
+            grads = ctx.fn._energy_grads(ctx.arrays, ctx.y, wrt, scale=grad_output.real) if wrt else [None] * len(ctx.arrays)
+            return (None,) * 5 + tuple(grads)
+
+    _EnergyFunction = EnergyFunction
+    return EnergyFunction
+
+
+class ApplyResult(collections.namedtuple("ApplyResult", "y norm exponent")):
+    """What ``HipContractor.apply_paulis`` returns: ``y = (sum over s of coeffs[s] P_s) x`` in the result's shape and
+    dtype (numpy for numpy inputs, a tensor on the device for ROCm torch inputs); ``norm`` = ``sum |x|^2`` of the
+    result ``x``; the base-10 ``exponent`` taken out under ``strip_exponent`` (0.0 otherwise: the true ``y`` is ``y
+    10^exponent``)."""
+
+    __slots__ = ()
+
+
+class EnergyResult(collections.namedtuple("EnergyResult", "energy values norm grads")):
+    """What ``HipContractor.energy`` returns: ``energy`` = ``sum over s of coeffs[s] values[s]`` (divided by ``norm``
+    under ``normalize``; a 0-d float64 tensor with a ``grad_fn`` under torch autograd); ``values`` the float64 array
+    of ``<x| P_s |x>`` per requested string, NOT normalised, the bits ``HipContractor.expectation`` returns (a 0-d
+    float for a single request); ``norm`` = ``sum |x|^2``; ``grads`` one gradient of ``energy`` per leaf -- ``d / d Re
+    x_i + i d / d Im x_i``, in the leaf's dtype and shape -- and ``None`` for a leaf outside ``wrt`` (``None``
+    altogether under autograd, which carries them)."""
+
+    __slots__ = ()
+
+
 class SampleResult(collections.namedtuple(
         "SampleResult", "indices coords amplitudes p norm sum_p2 max_p argmax exponent")):
     """What ``HipContractor.sample`` returns: ``indices`` ``(n,)`` int64 flat row-major positions in the result
@@ -1123,6 +1175,147 @@ class HipContractor:
                 norm = ex.result_stats()[0]
             exponent = ex.get_exponent()[0] if strip else 0.0
         return ExpectationResult(values=values if several else np.float64(values[0]), norm=norm, exponent=exponent)
+
+    # ---- a Pauli sum applied to the result, energies and their gradients ------------------- #
+
+    def apply_paulis(self, *arrays, paulis, coeffs=None, strip_exponent=False, check_zero=False, reuse=False):
+        """Contract (all slices, as a call does) and return ``y = (sum over s of coeffs[s] P_s) x`` of the result
+        ``x`` for the Pauli strings ``paulis`` over the output indices (:func:`pauli_requests`) and real ``coeffs``
+        (default: ones) -- formed on the device next to ``x``, which is not written (``ctg_exec_result_pauli_apply``,
+        DESIGN.md section 17).  ``y`` has the result's shape: numpy for numpy inputs, a tensor on the device for ROCm
+        torch inputs.  Returns an :class:`ApplyResult`.  ``ValueError`` -- before the device is touched -- for what
+        :func:`pauli_requests` refuses, ``coeffs`` of another length or not finite and, in a real contraction, a
+        string with an odd number of Y.  ``reuse=True``: as for :meth:`topk`; the result stays reusable."""
+        several, ops = pauli_requests(self.tree, paulis)
+        c = runtime.pauli_apply_coeffs(coeffs, len(ops))
+        if reuse and arrays:
+            raise ValueError("reuse=True reads the result of the call before: give no arrays.")
+        shape = tuple(int(d) for d in self.tree.gathered_shape())
+        if arrays:
+            runtime.pauli_apply_variant(_result_dtype(arrays), shape, ops)   # (odd Y in a real contraction)
+        with self._lock:
+            st, strip = self._reduce_state(arrays, strip_exponent, check_zero, reuse)
+            ex = st["exec"]
+            y = self._apply_on(st, shape, ops, c)
+            norm = ex.sample_info()[0] if len(ops) else ex.result_stats()[0]
+            exponent = ex.get_exponent()[0] if strip else 0.0
+        return ApplyResult(y=y, norm=norm, exponent=exponent)
+
+    @staticmethod
+    def _apply_on(st, shape, ops, coeffs):
+        """``y`` of ``Executor.pauli_apply_result`` for the executor state ``st``: a tensor next to a torch-owned
+        result (``dev_out``), numpy otherwise (``host_out``)."""
+        ex = st["exec"]
+        if "result" in st:
+            import torch
+
+            y = torch.empty(shape, dtype=st["result"].dtype, device=st["result"].device)
+            ex.pauli_apply_result(shape, ops, coeffs, out_ptr=y.data_ptr())
+            return y
+        return ex.pauli_apply_result(shape, ops, coeffs)
+
+    def _energy_forward(self, arrays, ops, coeffs, normalize):
+        """One contraction, the values of the strings and ``y`` with ``dE = 2 Re <y| dx>``: ``(energy, values, norm,
+        y)``; ``y`` has the result's shape and dtype (zeros when no string is left to apply)."""
+        shape = tuple(int(d) for d in self.tree.gathered_shape())
+        real = np.dtype(_result_dtype(arrays)).kind != "c"
+        with self._lock:
+            st, _ = self._reduce_state(arrays, False, False, False)
+            ex = st["exec"]
+            values = ex.pauli_result(shape, ops)
+            norm = ex.sample_info()[0] if len(values) else ex.result_stats()[0]
+            energy = 0.0
+            for c, v in zip(coeffs.tolist(), values.tolist()):
+                energy += c * v
+            use, cs = ops, coeffs
+            if real:
+                # (a string with an odd number of Y: its value and its gradient are exactly zero)
+                even = (ops == 2).sum(axis=1) % 2 == 0
+                use, cs = ops[even], coeffs[even]
+            if normalize:
+                if not norm > 0:
+                    raise ValueError("energy: normalize=True and the result has norm zero.")
+                energy = energy / norm
+                # d (E / N) = 2 Re <(H - (E / N) I) x / N | dx>
+                # (the identity term goes into the first all-identity string, if there is one: never more than the
+                # caller's strings plus one, which _energy_requests has checked)
+                cs = cs / norm
+                ident = np.flatnonzero(~use.any(axis=1))
+                if ident.size:
+                    cs[ident[0]] += -energy / norm
+                else:
+                    use = np.concatenate([use, np.zeros((1, ops.shape[1]), dtype=np.uint8)])
+                    cs = np.concatenate([cs, [-energy / norm]])
+            y = self._apply_on(st, shape, use, cs)
+        return energy, values, norm, y
+
+    def _energy_grads(self, arrays, y, wrt, scale=None):
+        """The VJP run of :meth:`energy`: cotangent ``conj(2 y)`` (times the real ``scale``), gradients conjugated
+        back (torch's convention for a real loss)."""
+        if _is_torch(y):
+            cot = (2.0 * y).conj().resolve_conj()
+            if scale is not None:
+                cot = cot * scale.to(device=cot.device, dtype=cot.real.dtype)
+        else:
+            cot = np.conj(2.0 * y)
+        grads = self.vjp(*arrays, cotangent=cot, wrt=wrt)
+        out = []
+        for g in grads:
+            if g is None:
+                out.append(None)
+            elif _is_torch(g):
+                out.append(g.conj().resolve_conj() if g.is_complex() else g)
+            else:
+                out.append(np.conj(g) if np.iscomplexobj(g) else g)
+        return out
+
+    def _energy_requests(self, paulis, coeffs, normalize):
+        """``(several?, ops, coeffs)`` of an energy request -- host only.  ``ValueError`` under ``strip_exponent``, for
+        what :func:`pauli_requests` and ``runtime.pauli_apply_coeffs`` refuse, and for ``normalize`` with
+        ``Executor.PAULI_MAX_STRINGS`` strings none of which is the identity: the apply call takes the identity term
+        of ``(H - (E / N) I) / N`` in the first all-identity string, or as one string more."""
+        if self.strip_exponent:
+            raise ValueError("energy does not support strip_exponent.")
+        several, ops = pauli_requests(self.tree, paulis)
+        c = runtime.pauli_apply_coeffs(coeffs, len(ops))
+        if normalize and len(ops) >= runtime.Executor.PAULI_MAX_STRINGS and ops.any(axis=1).all():
+            raise ValueError(f"energy: normalize=True adds an identity string to the {len(ops)} requests, none of which "
+                             f"is the identity; at most {runtime.Executor.PAULI_MAX_STRINGS} are taken by one call.")
+        return several, ops, c
+
+    def energy(self, *arrays, paulis, coeffs=None, wrt=None, normalize=False):
+        """Energy and gradient in one step on the device: ``E = sum over s of coeffs[s] <x| P_s |x>`` of the result
+        ``x`` and ``dE / d(every leaf)``.  One contraction; one ``ctg_exec_result_pauli`` call
+        for ``values`` (the bits :meth:`expectation` returns); ``energy`` is their sum with ``coeffs`` (default:
+        ones) in the caller's order on the host -- divided by ``norm`` under ``normalize``; one
+        ``ctg_exec_result_pauli_apply`` call forms ``y = H x`` (``(H - (E / N) I) x / N`` under ``normalize``) in a
+        device buffer; one VJP run with the cotangent ``conj(2 y)`` gives the gradients.  ``grads[i] = dE / d Re x_i +
+        i dE / d Im x_i`` (torch's convention for a real loss; ``dE / d x_i`` for a real leaf), in leaf ``i``'s dtype
+        and shape, ``None`` for a leaf outside ``wrt`` (default: all leaves).  In a real contraction a string with an
+        odd number of Y has value and gradient exactly zero and is left out of the apply call.  Works on sliced and
+        output-sliced trees.  Returns an :class:`EnergyResult`.  ``ValueError`` -- before the device is touched -- for
+        what :func:`pauli_requests` refuses, ``coeffs`` of another length or not finite, under ``strip_exponent``,
+        and for ``normalize`` with 4096 strings none of which is the identity (its identity term needs a string);
+        ``IndexError`` for ``wrt`` outside the leaves; ``ValueError`` for ``normalize`` with norm zero."""
+        several, ops, c = self._energy_requests(paulis, coeffs, normalize)
+        N = self.tree.N
+        wrt = tuple(range(N)) if wrt is None else tuple(sorted(set(int(i) for i in wrt)))
+        if wrt and (wrt[0] < 0 or wrt[-1] >= N):
+            raise IndexError(f"wrt {wrt} outside the {N} leaves")
+        with self._lock:
+            energy, values, norm, y = self._energy_forward(arrays, ops, c, normalize)
+            grads = self._energy_grads(arrays, y, wrt) if wrt else [None] * N
+        return EnergyResult(energy=energy, values=values if several else np.float64(values[0]), norm=norm, grads=grads)
+
+    def energy_autograd(self, *arrays, paulis, coeffs=None, normalize=False):
+        """:meth:`energy` under torch autograd: ``energy`` is a 0-d float64 tensor on the device with a ``grad_fn``
+        (the same bits as without autograd) and ``grads`` is ``None``; the forward saves ``y``, the backward runs the
+        one VJP plan for the inputs autograd asks for."""
+        several, ops, c = self._energy_requests(paulis, coeffs, normalize)
+        box = {}
+        energy = _energy_function().apply(self, ops, c, bool(normalize), box, *arrays)
+        values = box["values"]
+        return EnergyResult(energy=energy, values=values if several else np.float64(values[0]), norm=box["norm"], grads=None)
 
     def profile(self, arrays, slice_id=0):
         """Per-step milliseconds for one slice (see ``Plan.describe_steps``)."""

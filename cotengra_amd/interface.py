@@ -261,6 +261,14 @@ class ContractExpression:
         self._after_reduce()
         return out
 
+    def energy(self, *arrays, paulis, coeffs=None, wrt=None, normalize=False):
+        """``expr(*arrays)`` followed by the energy ``sum over s of coeffs[s] <x| P_s |x>`` of the result and its
+        gradient by the arrays ``wrt`` (default: all) on the device (``HipContractor.energy``, DESIGN.md section 17);
+        refused by an expression built with ``strip_exponent``."""
+        out = self.fn.energy(*arrays, paulis=paulis, coeffs=coeffs, wrt=wrt, normalize=normalize)
+        self._after_reduce()
+        return out
+
     def device_bytes(self):
         """Device memory this expression's executors hold right now (``ctg_exec_device_bytes``:
         arena x slice batch, inputs, tables, result, scratch), read under the contractor's lock

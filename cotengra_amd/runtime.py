@@ -55,6 +55,7 @@ SYMBOLS = (
     "ctg_exec_result_marginal",
     "ctg_exec_result_rdm",
     "ctg_exec_result_pauli",
+    "ctg_exec_result_pauli_apply",
     "ctg_exec_download_result",
     "ctg_exec_download_arena",
     "ctg_exec_get_state",
@@ -175,6 +176,7 @@ def load():
         "ctg_exec_result_marginal": [vp, C.c_int64, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_double)],
         "ctg_exec_result_rdm": [vp, C.c_int64, i64p, C.POINTER(C.c_int32), vp],
         "ctg_exec_result_pauli": [vp, C.c_int64, i64p, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_double)],
+        "ctg_exec_result_pauli_apply": [vp, C.c_int64, i64p, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_double), vp, vp],
         "ctg_exec_download_result": [vp, vp],
         "ctg_exec_download_arena": [vp, C.c_int64, C.c_int64, vp],
         "ctg_exec_get_state": [vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_int)],
@@ -348,6 +350,37 @@ def pauli_variant(dtype, extents, ops):
     if arr.shape[0] == 0 or (np.dtype(dtype).kind != "c" and bool(odd.all())):
         return "none"
     return f"pauli_chunk_kernel<{t}>" if _pauli_fast(ext, n) else f"pauli_general_kernel<{t}>"
+
+
+def pauli_apply_coeffs(coeffs, m):
+    """``coeffs`` of a Pauli-sum request as a float64 ``(m,)`` array (``None``: ones) -- host only: ``ValueError`` for
+    another length, a complex or non-numeric value and a coefficient that is not finite."""
+    if coeffs is None:
+        return np.ones(m, dtype=np.float64)
+    raw = np.asarray(coeffs)
+    if raw.dtype.kind not in "iufb":
+        raise ValueError(f"pauli_apply: coefficients of dtype {raw.dtype}; real numbers are expected.")
+    c = np.ascontiguousarray(raw, dtype=np.float64).reshape(-1)
+    if c.size != m:
+        raise ValueError(f"pauli_apply: {c.size} coefficients for {m} strings.")
+    if not np.all(np.isfinite(c)):
+        raise ValueError("pauli_apply: a coefficient is not finite.")
+    return c
+
+
+def pauli_apply_variant(dtype, extents, ops):
+    """The kernel ``ctg_exec_result_pauli_apply`` runs for a result of ``dtype`` and shape ``extents`` and the strings
+    ``ops`` -- a function of those alone (csrc/ctg_pauli_apply.hip): ``"pauli_apply_kernel<T>"`` on the power-of-two
+    route (every extent a power of two, at least 4096 elements), ``"pauli_apply_general_kernel<T>"`` otherwise; ``T``
+    one of ``float``, ``double``, ``c64``, ``c128``; ``"none"`` for no string (zeros are written without a kernel).
+    ``ValueError`` for what the call refuses, a string with an odd number of Y on a real ``dtype`` included."""
+    t = _DTYPE_TAG[np.dtype(dtype).name]
+    ext, n, arr = _pauli_ops(extents, ops)
+    if np.dtype(dtype).kind != "c" and bool(((arr == 2).sum(axis=1) % 2 == 1).any()):
+        raise ValueError("pauli_apply: a string with an odd number of Y on a real tensor: P x is not real.")
+    if arr.shape[0] == 0:
+        return "none"
+    return f"pauli_apply_kernel<{t}>" if _pauli_fast(ext, n) else f"pauli_apply_general_kernel<{t}>"
 
 
 class DevicePlan:
@@ -702,6 +735,32 @@ class Executor:
     def pauli_variant(self, extents, ops):
         """The name of the kernel ``pauli_result(extents, ops)`` runs on this executor (:func:`pauli_variant`)."""
         return pauli_variant(self.plan.dtype, extents, ops)
+
+    # -- a Pauli sum applied to the result tensor (csrc/ctg_pauli_apply.hip) -- #
+
+    def pauli_apply_result(self, extents, ops, coeffs, out_ptr=None):
+        """``y = (sum over s of coeffs[s] P_s) x`` of the result tensor ``x`` for the Pauli strings ``ops``
+        (``ctg_exec_result_pauli_apply``): ``extents`` and ``ops`` as for :meth:`pauli_result`, ``coeffs`` ``m`` real
+        numbers (``None``: ones).  Without ``out_ptr``: a numpy array of the result's shape and dtype.  With
+        ``out_ptr``, a device address of ``result_elems`` elements that does not overlap the result tensor: ``y`` is
+        written there and ``None`` returned.  The result tensor is not written.  ``ValueError`` for what
+        :meth:`pauli_result` refuses, for coefficients of another length or not finite, on a real plan for a string
+        with an odd number of Y (nothing is launched), and for a result whose ``sum p`` is not finite."""
+        ext, n, arr = _pauli_ops(extents, ops)
+        c = pauli_apply_coeffs(coeffs, arr.shape[0])
+        pauli_apply_variant(self.plan.dtype, ext, arr)   # (odd Y on a real plan)
+        e = np.ascontiguousarray(ext, dtype=np.int64).reshape(-1)
+        out = None if out_ptr else np.empty(tuple(ext), dtype=np.dtype(self.plan.dtype))
+        _check(load().ctg_exec_result_pauli_apply(
+            self.handle, e.size, _i64p(e), arr.shape[0], arr.ctypes.data_as(C.POINTER(C.c_uint8)),
+            c.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(int(out_ptr) if out_ptr else None),
+            C.c_void_p(None if out is None else out.ctypes.data)))
+        return out
+
+    def pauli_apply_variant(self, extents, ops):
+        """The name of the kernel ``pauli_apply_result(extents, ops, ...)`` runs on this executor
+        (:func:`pauli_apply_variant`)."""
+        return pauli_apply_variant(self.plan.dtype, extents, ops)
 
     # -- range audit (csrc/ctg_range.hip, cotengra_amd/rangeaudit.py) -- #
 

@@ -1111,6 +1111,28 @@ class ContractionTree:
 
         return _tree_contractor(self, order).expectation(*arrays, paulis=paulis, **kwargs)
 
+    def contract_apply_paulis(self, arrays, paulis, coeffs=None, order=None, **kwargs):
+        """:meth:`contract` followed by ``y = (sum over s of coeffs[s] P_s) x`` of the result ``x`` for the Pauli
+        strings ``paulis`` (as for :meth:`contract_expectation`) and real ``coeffs`` (default: ones), formed on the
+        device next to ``x`` (``HipContractor.apply_paulis``; ``kwargs``: ``strip_exponent``,
+        ``check_zero``, ``reuse``)."""
+        from .contractor import _tree_contractor
+
+        return _tree_contractor(self, order).apply_paulis(*arrays, paulis=paulis, coeffs=coeffs, **kwargs)
+
+    def contract_energy(self, arrays, paulis, coeffs=None, wrt=None, normalize=False, order=None):
+        """:meth:`contract` followed by the energy ``sum over s of coeffs[s] <x| P_s |x>`` of the result and its
+        gradient by the leaves ``wrt`` (default: all), everything on the device: the values of the strings, ``H x`` and
+        one VJP run (``HipContractor.energy``).  With ROCm tensors that require grad under grad
+        mode ``energy`` is a 0-d float64 tensor on the device with a ``grad_fn`` (the same bits) and ``grads`` is
+        ``None``: ``backward`` runs the VJP plan (``wrt`` is autograd's then)."""
+        from .contractor import _tree_contractor, _wants_grad
+
+        fn = _tree_contractor(self, order)
+        if _wants_grad(arrays):
+            return fn.energy_autograd(*arrays, paulis=paulis, coeffs=coeffs, normalize=normalize)
+        return fn.energy(*arrays, paulis=paulis, coeffs=coeffs, wrt=wrt, normalize=normalize)
+
     def contract_audit(self, arrays, slices=(0,), order=None):
         """Range audit of the contraction on ``arrays`` (``HipContractor.audit``): the
         slices ``slices`` run step by step, one record per plan step with the exponent statistics of its

@@ -515,6 +515,42 @@ int ctg_exec_result_rdm(ctg_exec* exec, int64_t rank, const int64_t* extents, co
  * holds the total and the call works there (untested). */
 #define CTG_PAULI_MAX_STRINGS 4096
 int ctg_exec_result_pauli(ctg_exec* exec, int64_t rank, const int64_t* extents, int64_t m, const uint8_t* ops, double* out);
+/* Added to ABI 10 WITHOUT a bump of CTG_ABI_VERSION likewise (one new symbol; a binding that needs it looks it up):
+ * y = (sum over s of coeffs[s] P_s) x for Pauli strings P_s over the axes of the result tensor x, written on the device
+ * (csrc/ctg_pauli_apply.hip).  H = sum c_s P_s is Hermitian and the contraction is holomorphic in
+ * its leaves, so conj(2 y) is the cotangent of E = <x| H |x> for a VJP plan: energy and gradient stay on the device.
+ * extents, ops[m * rank] and the codes 0 .. 3 are those of ctg_exec_result_pauli; coeffs[m] are real.  With xm the
+ * flat-index bits of the X and Y axes of a string, zm those of its Z and Y axes and ny its number of Y,
+ *   (P x)[j] = i^ny (-1)^popcount((j ^ xm) & zm) x[j ^ xm],     y[j] = sum over s of coeffs[s] (P_s x)[j],
+ * result_elems elements of the plan's dtype, written to dev_out (device memory that does not overlap the result
+ * tensor), to host_out (a synchronous copy) or to both; with host_out alone y is staged in the scratch of the calls
+ * above (counted by ctg_exec_device_bytes, freed by ctg_exec_destroy).  The tensor is read as the calls above read it
+ * (whoever owns the memory, the mantissa under strip_exponent, after the stream's earlier work, after the statistics
+ * passes, which run first) and never written; the stream is synchronised.  CTG_E_NORM when sum p is not finite; an
+ * all-zero tensor gives zeros.  CTG_E_INVALID -- checked on the host before anything is launched, the tensor and both
+ * buffers untouched -- for everything ctg_exec_result_pauli refuses (out aside), null coeffs with m > 0, both outputs
+ * null, a dev_out that overlaps the result tensor, a coefficient that is not finite and, on real plans, a string with
+ * an odd number of Y (P x is not real).  m = 0 writes zeros.  m <= CTG_PAULI_MAX_STRINGS.
+ *   - Arithmetic: the strings are grouped by their X / Y axis set (xm), groups in order of first appearance, the
+ *     caller's order inside a group.  Per element j and group g a complex fp64 weight W starts at 0 and takes, string
+ *     after string, +-coeffs[s]: into Re W for even ny, Im W for odd ny, negative when the parity of popcount(j & zm)
+ *     and of (ny mod 4 in {1, 2}) differ.  Then, with p = x[j ^ xm_g] in fp64: acc_re += (Re W p_re - Im W p_im),
+ *     acc_im += (Re W p_im + Im W p_re) -- four products, the difference / sum and the addition each rounded once,
+ *     nothing fused; real plans: acc += W p.  After the last group acc is rounded once to the plan's dtype.
+ *   - No atomics and no sum across threads: the bits of y are a function of (dtype, extents, ops in order, coeffs, the
+ *     tensor's bytes) alone -- not of the executor, the grid, earlier calls in the scratch, or which output was asked.
+ *   - Per real component |y[j] - exact| <= (m + 2) 2^-53 sum over s of |c_s| (|Re| + |Im|)(x[j ^ xm_s]) + u |y[j]|,
+ *     u = 2^-24 for float / complex64 plans and 2^-53 for double / complex128 (first order).
+ * Every extent a power of two and at least 4096 elements: "pauli_apply_kernel<T>", T in float | double | c64 | c128, one
+ * launch: a workgroup takes the output chunks wg, wg + grid, ... of 4096 elements, grid = min(512, ceil(chunks / 3)); a
+ * thread keeps 16 elements' acc and W in fp64 registers; a group's strings run in passes of 32, one sign word per
+ * (element, pass); the partner chunk c ^ (xm >> 12) is read once per group, straight into registers or through an LDS
+ * copy; y is written with one 16-byte store per lane and 16-byte group.  Any other shape:
+ * "pauli_apply_general_kernel<T>", a thread per output element, same groups and order; not tuned.  Scratch: 1640 bytes
+ * per pass (general route: 24 per group, 24 per string, 8 per non-identity letter) plus the staged y.  No multi-rank
+ * entry: after ctg_exec_reduce the root's result tensor holds the total and the call works there (untested). */
+int ctg_exec_result_pauli_apply(ctg_exec* exec, int64_t rank, const int64_t* extents, int64_t m, const uint8_t* ops,
+                                const double* coeffs, void* dev_out, void* host_out);
 /* debugging aid: copy `n` elements of the arena starting at element `offset`
  * to the host (synchronous) */
 int ctg_exec_download_arena(ctg_exec* exec, int64_t offset, int64_t n, void* host_out);
