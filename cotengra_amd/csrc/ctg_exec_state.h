@@ -115,6 +115,7 @@ struct ctg_exec {
     // runs it (-1: none, the step launches as usual); components sorted [group-shared..., per-slice...]
     std::vector<int32_t> lds_comp_of;
     int lds_first[2] = {0, 0}, lds_count[2] = {0, 0}, lds_bytes[2] = {0, 0};   // [0] group-shared, [1] per slice
+    std::vector<std::vector<ctg::LdsForm>> lds_forms;   // per packed component, in record order (ctg_exec_lds_form)
     ctg::LdsCompDev* d_lds_comps = nullptr;
     char* d_lds_blob = nullptr;
     ctg::ValuGroupItem* d_group_items = nullptr;

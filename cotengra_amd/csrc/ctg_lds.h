@@ -60,6 +60,20 @@ struct LdsCompDev {
     uint32_t pad;
 };
 
+// The form a shadow record takes inside the launch, as lds_record_form (ctg_lds_host.hip) decides it for the packer
+// and for the name the executor reports (ctg_exec_lds_form).
+struct LdsForm {
+    int32_t kind;       // 0 load, 1 pair
+    int32_t sum;        // loads: 0 a plain gather (K = 1), 1 a gather-and-sum
+    int32_t tn;         // VALU pairs: the columns a lane computes, run_pair<T, 1 | 2 | 4>
+    int32_t mfma;       // pairs: 0 VALU, 1 matrix cores with columns on the lanes, 2 with rows on the lanes
+    int32_t wave;       // the wave the record is dealt to, -1: shared by the workgroup
+    int32_t rot;        // matrix-core records shared by the workgroup: the start rotation
+    int32_t shift;      // row division: log2(row_lo), or -1 for the multiply-high form
+    uint32_t magic;     // ... floor(2^32 / row_lo) + 1 then, else 0
+    int64_t main;       // the ordinary step the record belongs to
+};
+
 // n_comps workgroups x nz slices of the batch (ctg_lds_run.hip)
 hipError_t launch_lds_run(int dtype, const LdsCompDev* d_comps, int n_comps, int nz, int z0, int lds_bytes, hipStream_t stream);
 

@@ -55,7 +55,101 @@ int log2_of(int64_t v) {
     return s;
 }
 
+// What the records of one component have been dealt so far, per phase: the load of every wave, and the tiles of the
+// phase's earlier matrix-core records (the next one's start rotation).
+struct LdsDeal {
+    std::map<int64_t, std::vector<int64_t>> wave_load;
+    std::map<int64_t, int64_t> mfma_rot;
+};
+
+// The form record `q` of a component descriptor takes inside lds_run_kernel -- the one place that decides it, for the
+// packer (ctg_lds_build) and for the name the executor reports (ctg_exec_lds_form).  Records are asked in order:
+// `deal` carries what the earlier ones of the component were given.  false: the packer refuses the record (its
+// component stays off).
+bool lds_record_form(const ctg_plan* p, const int64_t* q, bool no_mfma, LdsDeal& deal, LdsForm* f) {
+    bool ok = true;
+    const int64_t kind = q[LR_KIND], R = q[LR_R], K = q[LR_K], N = q[LR_N];
+    const int64_t row_hi = q[LR_ROW_HI_LEN], row_lo = q[LR_ROW_LO];
+    f->kind = (int32_t)kind;
+    f->main = q[LR_MAIN];
+    f->sum = kind == 0 && K != 1 ? 1 : 0;
+    // rows are two-level, r -> (r / row_lo, r % row_lo): a shift, or the high half of r * (floor(2^32 / row_lo) + 1),
+    // which is the quotient for every r < 2^16
+    f->shift = log2_of(row_lo);
+    f->magic = 0;
+    if (f->shift < 0) {
+        if (R >= 65536) ok = false;
+        f->magic = (uint32_t)((1ull << 32) / (uint64_t)row_lo) + 1u;
+    }
+    // matrix cores: complex64 GEMM-like pair steps with enough rows and columns to fill a good part of a
+    // 32 x 16 tile (B must not depend on the row: no batch index)
+    f->mfma = 0;
+    if (kind == 1 && p->dtype == CTG_C64 && N >= 8 && R >= 16 && !no_mfma) {
+        bool gemm = true;
+        for (int64_t j = 0; j < row_hi && gemm; ++j) gemm = p->tables[q[LR_ROWB_HI] + j] == 0;
+        for (int64_t j = 0; j < row_lo && gemm; ++j) gemm = p->tables[q[LR_ROWB_LO] + j] == 0;
+        f->mfma = gemm ? 1 : 0;
+        if (gemm) {
+            // which way the result is stored: the lanes of a store run along the index group that is
+            // denser in C (1: columns on the lanes, 2: rows on the lanes)
+            auto stride = [&](int64_t w, int64_t len) -> int64_t {
+                return len > 1 ? std::llabs(p->tables[w + 1] - p->tables[w]) : INT64_MAX;
+            };
+            const int64_t srow = stride(q[LR_ROWC_LO], row_lo), scol = stride(q[LR_NC], N);
+            if (srow <= scol) f->mfma = 2;
+        }
+    }
+    // wave assignment
+    const int tn = N >= 3 ? 4 : (int)N;
+    f->tn = kind == 1 && !f->mfma ? tn : 0;
+    int64_t items = kind == 1 ? R * ((N + tn - 1) / tn) : R;
+    const int64_t tasks = ((R + 31) / 32) * ((N + 15) / 16);
+    if (f->mfma) items = tasks <= 1 ? 1 : 1 << 20;
+    // (loads: one wave each, so that the gathers of a component's leaves are all in flight together)
+    if (kind == 0 && items <= 4096) items = std::min<int64_t>(items, 128);
+    f->wave = -1;
+    f->rot = 0;
+    if (f->mfma && tasks > 1) {
+        int64_t& rot = deal.mfma_rot[q[LR_PHASE]];
+        f->rot = (int32_t)(rot % (LDS_RUN_THREADS / 64));
+        rot += tasks;
+    }
+    if (items <= 128) {
+        std::vector<int64_t>& load = deal.wave_load[q[LR_PHASE]];
+        if (load.empty()) load.assign(LDS_RUN_THREADS / 64, 0);
+        const int w = (int)(std::min_element(load.begin(), load.end()) - load.begin());
+        load[(size_t)w] += 64 + items * K * tn;
+        f->wave = w;
+    }
+    return ok;
+}
+
+// "load<gather|sum>", "pair<1|2|4>" or "pair_mfma<cols|rows>"; then "wave=W" (dealt to one wave) or "all" (shared by
+// the workgroup; matrix-core records: "all rot=R"); then "shift" or "magic", the row division.
+void lds_form_name(const LdsForm& f, char* buf, size_t len) {
+    char head[32], deal[32];
+    if (f.kind == 0) snprintf(head, sizeof(head), "load<%s>", f.sum ? "sum" : "gather");
+    else if (f.mfma) snprintf(head, sizeof(head), "pair_mfma<%s>", f.mfma == 2 ? "rows" : "cols");
+    else snprintf(head, sizeof(head), "pair<%d>", (int)f.tn);
+    if (f.wave >= 0) snprintf(deal, sizeof(deal), "wave=%d", (int)f.wave);
+    else if (f.mfma) snprintf(deal, sizeof(deal), "all rot=%d", (int)f.rot);
+    else snprintf(deal, sizeof(deal), "all");
+    snprintf(buf, len, "%s %s %s", head, deal, f.shift >= 0 ? "shift" : "magic");
+}
+
 }  // namespace
+
+int ctg_exec_lds_form(ctg_exec* e, int64_t comp, int64_t rec, int64_t* main_step, char* buf, int64_t buflen) {
+    if (!e || !main_step || !buf || buflen < 1) return lfail(CTG_E_INVALID, "null argument");
+    if (comp < 0 || rec < 0) return lfail(CTG_E_INVALID, "negative component or record");
+    *main_step = -1;
+    buf[0] = 0;
+    if ((size_t)comp >= e->lds_forms.size() || (size_t)rec >= e->lds_forms[(size_t)comp].size()) return CTG_OK;
+    const LdsForm& f = e->lds_forms[(size_t)comp][(size_t)rec];
+    *main_step = f.main;
+    lds_form_name(f, buf, (size_t)buflen);
+    return CTG_OK;
+}
 
 // Every component descriptor the step records point at: structure, table ranges, that every LDS address
 // stays inside the component's data area and every global address inside its space.
@@ -181,6 +275,7 @@ int ctg_lds_build(ctg_exec* e) {
     if (e->d_lds_blob) (void)hipFree(e->d_lds_blob);
     e->d_lds_comps = nullptr;
     e->d_lds_blob = nullptr;
+    e->lds_forms.clear();
     // (strip_exponent keeps a scale per step: the ordinary steps run)
     if (e->strip || env_on("CTG_NO_LDS_RUNS")) return CTG_OK;
     std::map<int64_t, int64_t> comp_desc;
@@ -189,7 +284,7 @@ int ctg_lds_build(ctg_exec* e) {
         if (r[W_LDS_COMP] > 0) comp_desc[r[W_LDS_COMP] - 1] = r[W_LDS_DESC];
     }
     if (comp_desc.empty()) return CTG_OK;
-    struct Packed { int64_t cid; std::vector<char> blob; uint32_t n_steps, data_off; int lds_bytes; bool shared; };
+    struct Packed { int64_t cid; std::vector<char> blob; std::vector<LdsForm> forms; uint32_t n_steps, data_off; int lds_bytes; bool shared; };
     const bool no_mfma = env_on("CTG_LDS_NO_MFMA");
     std::vector<Packed> packed;
     for (const auto& cd : comp_desc) {
@@ -209,8 +304,8 @@ int ctg_lds_build(ctg_exec* e) {
         };
         const size_t rec_bytes = (size_t)n_rec * sizeof(LdsStepDev);
         // per phase: small steps are dealt to single waves (least loaded first), large ones shared by all
-        std::map<int64_t, std::vector<int64_t>> wave_load;
-        std::map<int64_t, int64_t> mfma_rot;
+        LdsDeal deal;
+        std::vector<LdsForm>& forms = pk.forms;
         pk.shared = false;
         for (int64_t i = 0; i < n_rec && ok; ++i) {
             const int64_t* q = h + LR_HEAD_WORDS + i * LR_WORDS;
@@ -226,12 +321,15 @@ int ctg_lds_build(ctg_exec* e) {
             st.K = (int32_t)q[LR_K];
             st.N = (int32_t)q[LR_N];
             st.row_lo = (int32_t)q[LR_ROW_LO];
-            st.row_shift = log2_of(q[LR_ROW_LO]);
-            st.row_magic = 0;
-            if (st.row_shift < 0) {
-                if (q[LR_R] >= 65536) ok = false;
-                st.row_magic = (uint32_t)((1ull << 32) / (uint64_t)q[LR_ROW_LO]) + 1u;
-            }
+            // the form of the record: row division, VALU or matrix cores, dealt or shared, start rotation
+            LdsForm form;
+            if (!lds_record_form(p, q, no_mfma, deal, &form)) ok = false;
+            forms.push_back(form);
+            st.row_shift = form.shift;
+            st.row_magic = form.magic;
+            st.mfma = form.mfma;
+            st.wave = form.wave;
+            st.rot = form.rot;
             st.a_off = q[LR_A_LDS] ? (int32_t)q[LR_A_OFF] : -1;
             st.b_off = (kind == 1 && q[LR_B_LDS]) ? (int32_t)q[LR_B_OFF] : -1;
             st.c_off = q[LR_C_LDS] ? (int32_t)q[LR_C_OFF] : -1;
@@ -287,45 +385,6 @@ int ctg_lds_build(ctg_exec* e) {
                 else if (gop == 1) { st.gptr = (const char*)a.B; st.gsoff = a.soffB; st.gz = a.zB; st.gzs = (int32_t)a.zsB; st.gzq = a.zqB; }
                 else { st.gptr = (const char*)a.C; st.gsoff = a.soffC; st.gz = a.zC; st.gzs = (int32_t)a.zsC; st.gzq = 0; }
             }
-            // matrix cores: complex64 GEMM-like pair steps with enough rows and columns to fill a good part of a
-            // 32 x 16 tile (B must not depend on the row: no batch index)
-            st.mfma = 0;
-            if (kind == 1 && p->dtype == CTG_C64 && q[LR_N] >= 8 && q[LR_R] >= 16 && !no_mfma) {
-                bool gemm = true;
-                for (int64_t j = 0; j < row_hi && gemm; ++j) gemm = p->tables[q[LR_ROWB_HI] + j] == 0;
-                for (int64_t j = 0; j < row_lo && gemm; ++j) gemm = p->tables[q[LR_ROWB_LO] + j] == 0;
-                st.mfma = gemm ? 1 : 0;
-                if (gemm) {
-                    // which way the result is stored: the lanes of a store run along the index group that is
-                    // denser in C (1: columns on the lanes, 2: rows on the lanes)
-                    auto stride = [&](int64_t w, int64_t len) -> int64_t {
-                        return len > 1 ? std::llabs(p->tables[w + 1] - p->tables[w]) : INT64_MAX;
-                    };
-                    const int64_t srow = stride(q[LR_ROWC_LO], row_lo), scol = stride(q[LR_NC], q[LR_N]);
-                    if (srow <= scol) st.mfma = 2;
-                }
-            }
-            // wave assignment
-            const int tn = q[LR_N] >= 3 ? 4 : (int)q[LR_N];
-            int64_t items = kind == 1 ? q[LR_R] * ((q[LR_N] + tn - 1) / tn) : q[LR_R];
-            const int64_t tasks = ((q[LR_R] + 31) / 32) * ((q[LR_N] + 15) / 16);
-            if (st.mfma) items = tasks <= 1 ? 1 : 1 << 20;
-            // (loads: one wave each, so that the gathers of a component's leaves are all in flight together)
-            if (kind == 0 && items <= 4096) items = std::min<int64_t>(items, 128);
-            st.wave = -1;
-            st.rot = 0;
-            if (st.mfma && tasks > 1) {
-                int64_t& rot = mfma_rot[q[LR_PHASE]];
-                st.rot = (int32_t)(rot % (LDS_RUN_THREADS / 64));
-                rot += tasks;
-            }
-            if (items <= 128) {
-                std::vector<int64_t>& load = wave_load[q[LR_PHASE]];
-                if (load.empty()) load.assign(LDS_RUN_THREADS / 64, 0);
-                const int w = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-                load[(size_t)w] += 64 + items * q[LR_K] * tn;
-                st.wave = w;
-            }
         }
         if (!ok) continue;
         // table offsets are relative to the blob: records first
@@ -373,6 +432,7 @@ int ctg_lds_build(ctg_exec* e) {
         if (e->lds_count[cls] == 0) e->lds_first[cls] = (int)i;
         e->lds_count[cls] += 1;
         e->lds_bytes[cls] = std::max(e->lds_bytes[cls], pk.lds_bytes);
+        e->lds_forms.push_back(pk.forms);
         for (int64_t s = 0; s < p->n_steps; ++s)
             if (p->steps[s * STEP_WORDS + W_LDS_COMP] == pk.cid + 1) e->lds_comp_of[s] = (int32_t)i;
     }

@@ -19,9 +19,12 @@
 // A pair step: lane = one row r (consecutive lanes = consecutive rows) x TN columns.  The rows operand
 // is stored [contracted..., rows...] by its producer, so the 64 lanes of a wavefront read 64 consecutive
 // LDS words at every k (conflict-free); the other operand is read as a broadcast.  Small steps of one
-// phase are dealt to single wavefronts (they run side by side), large ones are shared by all eight.
-// The arithmetic is pair_valu_kernel's: one accumulator per output, k ascending, fused multiply-adds --
-// a component gives the same bits as its steps launched one by one on that kernel.
+// phase are dealt to single wavefronts (they run side by side), large ones are shared by all sixteen
+// (LDS_RUN_THREADS = 1024).  The arithmetic is pair_valu_kernel's: one accumulator per output, k ascending,
+// fused multiply-adds -- a component gives the same bits as its steps launched one by one on that kernel.
+// Which form a record takes -- load or pair, columns per lane, matrix cores, dealt or shared, row division --
+// is decided by lds_record_form (ctg_lds_host.hip) and reported by ctg_exec_lds_form; one row per form:
+// tests/lds_variant_cases.py.
 #include <algorithm>
 #include <cstdio>
 #include <vector>

@@ -42,6 +42,7 @@ SYMBOLS = (
     "ctg_exec_launch_count",
     "ctg_exec_profile_slice",
     "ctg_exec_step_kernel",
+    "ctg_exec_lds_form",
     "ctg_exec_step_paired_stores",
     "ctg_exec_step_stem_max",
     "ctg_plan_stem_pair16",
@@ -162,6 +163,7 @@ def load():
         "ctg_exec_launch_count": [vp, i64p, i64p],
         "ctg_exec_profile_slice": [vp, C.c_int64, C.POINTER(C.c_float)],
         "ctg_exec_step_kernel": [vp, C.c_int64, C.c_char_p, C.c_int64],
+        "ctg_exec_lds_form": [vp, C.c_int64, C.c_int64, i64p, C.c_char_p, C.c_int64],
         "ctg_exec_step_paired_stores": [vp, C.c_int64, C.POINTER(C.c_int)],
         "ctg_exec_step_stem_max": [vp, C.c_int64, C.c_int64, C.POINTER(C.c_float)],
         "ctg_plan_stem_pair16": [vp, C.c_int64, C.POINTER(C.c_int)],
@@ -587,6 +589,27 @@ class Executor:
             _check(load().ctg_exec_step_kernel(self.handle, s, buf, 160))
             names.append(buf.value.decode())
         return names
+
+    def lds_forms(self):
+        """Per packed LDS-resident subtree (the ``c`` of ``lds_run_kernel[c]`` in :meth:`step_kernels`), in the order
+        its workgroup walks them, one ``(name, step)`` per shadow record: the form the record takes inside the launch
+        (``ctg_exec_lds_form``: ``load<gather|sum>``, ``pair<1|2|4>`` or ``pair_mfma<cols|rows>``; ``wave=W`` or
+        ``all``, matrix-core records ``all rot=R``; ``shift`` or ``magic``) and the plan step it belongs to.  A subtree
+        the packer left off is not in the list."""
+        fn = load().ctg_exec_lds_form
+        buf = C.create_string_buffer(96)
+        main = C.c_int64()
+        out = []
+        while True:
+            recs = []
+            while True:
+                _check(fn(self.handle, len(out), len(recs), C.byref(main), buf, 96))
+                if main.value < 0:
+                    break
+                recs.append((buf.value.decode(), int(main.value)))
+            if not recs:
+                return out
+            out.append(recs)
 
     def step_paired_stores(self):
         """Per plan step: did its last launch store two adjacent columns of a row as one 16-byte store

@@ -331,6 +331,21 @@ int ctg_exec_profile_slice(ctg_exec* exec, int64_t slice_id, float* ms);
  *   "pair_pick_rows_mfma_kernel<c64>"                        matrix-core form (row_lo >= 32, N >= 8, K >= 8)
  * Match by prefix. */
 int ctg_exec_step_kernel(ctg_exec* exec, int64_t step, char* buf, int64_t buflen);
+/* Added to ABI 10 WITHOUT a bump of CTG_ABI_VERSION: one new symbol, nothing else changes.
+ * The members of an LDS-resident subtree are all "lds_run_kernel[c]" above; inside that launch every shadow record of
+ * packed component c takes one of several forms, decided by the packer.  Record `rec` (in the order the workgroup
+ * walks them) of component `comp` is
+ *   "load<gather|sum> DEAL DIV"          global -> LDS: a plain gather (K = 1), or a gather that sums (leaf trace /
+ *                                        diagonal / sum)
+ *   "pair<1|2|4> DEAL DIV"               a pair step on the vector units, 1, 2 or 4 columns per lane
+ *   "pair_mfma<cols|rows> DEAL DIV"      a complex64 pair step on the matrix cores, columns or rows on the lanes
+ * DEAL is "wave=W", the one wave the record is dealt to, or "all", shared by the workgroup's sixteen waves -- a
+ * matrix-core record then "all rot=R", the wave its first tile goes to; DIV is "shift" or "magic", how a row number
+ * is divided by the length of the low row table (a shift; or the high half of a product with
+ * floor(2^32 / row_lo) + 1).  *main_step is the plan step the record belongs to.  A record past the component's last,
+ * and a component past the last packed one -- which includes every component the packer left off (CTG_NO_LDS_RUNS,
+ * strip_exponent, a blob that does not fit) --, gives an empty name and *main_step = -1. */
+int ctg_exec_lds_form(ctg_exec* exec, int64_t comp, int64_t rec, int64_t* main_step, char* buf, int64_t buflen);
 /* Added to ABI 10 WITHOUT a bump of CTG_ABI_VERSION: THREE new symbols, nothing else changes -- a plan, an executor and
  * every existing call behave as before, which is the rule by which ABI 10 has grown (kernel codes 2 and 3, top-k,
  * marginals, reduced density matrices); the binding binds them like every other symbol.

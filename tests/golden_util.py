@@ -177,6 +177,34 @@ def pair_flags_c64(name):
     return out
 
 
+def lds_form(name):
+    """What the executor says of one shadow record of an LDS-resident subtree (include/ctg_hip.h: ctg_exec_lds_form,
+    ``Executor.lds_forms()``): ``kernel``, "load", "pair" or "pair_mfma"; ``arg``, "gather" | "sum", the columns per
+    lane 1 | 2 | 4, or "cols" | "rows"; ``wave``, the wave the record is dealt to or -1 when the workgroup shares it;
+    ``rot``, the start rotation of a shared matrix-core record (None elsewhere); ``magic``, whether rows are divided by
+    the multiply-high (False: a shift)."""
+    parts = name.split(" ")
+    head, div = parts[0], parts[-1]
+    kernel, arg = head[:-1].split("<")
+    assert head.endswith(">") and div in ("shift", "magic"), name
+    assert (kernel, arg) in [("load", "gather"), ("load", "sum"), ("pair", "1"), ("pair", "2"), ("pair", "4"),
+                             ("pair_mfma", "cols"), ("pair_mfma", "rows")], name
+    out = {"kernel": kernel, "arg": int(arg) if kernel == "pair" else arg, "wave": -1, "rot": None, "magic": div == "magic"}
+    deal = parts[1:-1]
+    if deal[0] == "all":
+        if kernel == "pair_mfma":
+            assert len(deal) == 2 and deal[1].startswith("rot="), name
+            out["rot"] = int(deal[1][4:])
+            assert 0 <= out["rot"] < 16, name
+        else:
+            assert len(deal) == 1, name
+    else:
+        assert len(deal) == 1 and deal[0].startswith("wave="), name
+        out["wave"] = int(deal[0][5:])
+        assert 0 <= out["wave"] < 16, name
+    return out
+
+
 def stem_network(nq, gates, seed, sliced=0):
     """A small 'stem': one tensor of ``nq`` binary indices to which tensors are
     applied one after the other, gate ``(k, n)`` contracting ``k`` randomly chosen
