@@ -604,6 +604,9 @@ int stem2_last_paired();    // did the last launch_stem2 / launch_stem2h take th
 int stem2h_last_paired();
 
 hipError_t launch_single(int dtype, const StepArgs& p, hipStream_t stream);
+// the kernel that launch takes for this step: "single_wave_kernel" (a wave per output: K >= 256 and R <= 2^14) or
+// "single_kernel" (a thread per output)
+void single_name(const StepArgs& p, char* buf, size_t n);
 bool pair_bf16x3_on(const StepArgs& p);   // (ctg_pair_mfma.hip) do long tiled steps multiply with bf16 x 3 products right now?
 // ``leaf``: the input whose own upload shift the coefficient leaves out (a gradient's accumulate, ABI 8), -1: none
 hipError_t launch_accum(int dtype, const StepArgs& p, const StripState* st, void* wide, const double* inscale, int leaf,
@@ -630,6 +633,8 @@ hipError_t launch_narrow(int dtype, void* result, const void* wide, int64_t n, h
 hipError_t launch_widen(int dtype, void* wide, const void* result, int64_t n, hipStream_t stream);
 
 hipError_t launch_maxabs(int dtype, const void* x, int64_t n, double* fac, hipStream_t stream);
+// *fac <- max(*fac, largest |element| of what accumulate step `p` adds: its source rows, every slice of the launch)
+hipError_t launch_accum_source_maxabs(int dtype, const StepArgs& p, double* fac, hipStream_t stream);
 // e_slice = sum_s log10(fac[s]) over the listed steps; coefficients for the accumulate
 hipError_t launch_strip_prepare(const double* fac, const int32_t* counted, int64_t n_steps,
                                 int64_t root_step, int check_zero, StripState* st, const double* inscale, hipStream_t stream);

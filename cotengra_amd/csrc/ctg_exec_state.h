@@ -136,8 +136,11 @@ struct ctg_exec {
     // strip_exponent state
     int strip = 0, check_zero = 0;
     double* d_fac = nullptr;        // [n_steps + 1] max|.| per pair step; last = constant 1.0
-    int32_t* d_counted = nullptr;   // [n_steps] 1 for pair steps
+    int32_t* d_counted = nullptr;   // [n_steps] 1 for pair steps; 2: the zero test alone (zero_probe_step)
     int32_t* d_fac_zero = nullptr;  // [n_steps] 1 for per-slice pair steps
+    // the accumulate step of a plan without a pair step (a one-input tree), -1 otherwise: nothing is normalised there,
+    // but check_zero still looks for a zero slice -- a max-abs pass over what the step adds fills its slot of d_fac
+    int64_t zero_probe_step = -1;
     // slice-invariant steps: executed once per upload / option change
     std::vector<char> invariant;
     bool invariants_ready = false;

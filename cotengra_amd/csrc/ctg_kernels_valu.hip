@@ -415,9 +415,14 @@ __global__ __launch_bounds__(256) void single_wave_kernel(StepArgs p) {
     }
 }
 
+// The route of a step through launch_single_t, the one place that decides it for the launcher and for the name the
+// executor reports (ctg_exec_step_kernel): few outputs under a long sum put lanes along the summed group (one wave
+// per output), everything else is a thread per output.
+static bool single_route_wave(const StepArgs& p) { return p.K >= 256 && p.R <= (1 << 14); }
+
 template <typename T>
 static hipError_t launch_single_t(const StepArgs& p, hipStream_t stream) {
-    if (p.K >= 256 && p.R <= (1 << 14)) {
+    if (single_route_wave(p)) {
         int64_t blocks = (p.R + 3) / 4;
         if (blocks < 1) blocks = 1;
         hipLaunchKernelGGL(single_wave_kernel<T>, dim3((unsigned)blocks, (unsigned)p.nz), dim3(256), 0, stream, p);
@@ -438,6 +443,10 @@ hipError_t launch_single(int dtype, const StepArgs& p, hipStream_t stream) {
         case 3: return launch_single_t<c128>(p, stream);
     }
     return hipErrorInvalidValue;
+}
+
+void single_name(const StepArgs& p, char* buf, size_t n) {
+    snprintf(buf, n, single_route_wave(p) ? "single_wave_kernel" : "single_kernel");
 }
 
 // ------------------------------------------------------------------------- //
@@ -735,6 +744,45 @@ hipError_t launch_maxabs(int dtype, const void* x, int64_t n, double* fac, hipSt
     return hipGetLastError();
 }
 
+// The same of what an accumulate step adds -- its source rows, addressed as accum_rows addresses them, every slice of
+// the launch: the zero test of check_zero in a plan without a pair step (a one-input tree), whose slice output no
+// other max-abs pass sees.
+template <typename T>
+__global__ __launch_bounds__(256) void accum_source_maxabs_kernel(StepArgs p, double* fac) {
+    double m = 0.0;
+    const int64_t z_end = (int64_t)p.z0 + p.nz;
+    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < p.R; row += (int64_t)gridDim.x * 256) {
+        int64_t hi, lo;
+        split_row(p, row, hi, lo);
+        const int64_t ra = p.rowA.hi[hi] + p.rowA.lo[lo];
+        for (int64_t z = p.z0; z < z_end; ++z) {
+            const double a = abs_of(((const T*)p.A + p.soffA[z * p.zsA] + z * p.zA)[ra]);
+            m = a > m || a != a ? a : m;  // propagate nan
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double other = __shfl_down(m, o, 64);
+        m = other > m || other != other ? other : m;
+    }
+    if ((threadIdx.x & 63) == 0)
+        atomicMax((unsigned long long*)fac, (unsigned long long)__double_as_longlong(m));
+}
+
+hipError_t launch_accum_source_maxabs(int dtype, const StepArgs& p, double* fac, hipStream_t stream) {
+    int64_t blocks = (p.R + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    switch (dtype) {
+        case 0: hipLaunchKernelGGL(accum_source_maxabs_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, stream, p, fac); break;
+        case 1: hipLaunchKernelGGL(accum_source_maxabs_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, stream, p, fac); break;
+        case 2: hipLaunchKernelGGL(accum_source_maxabs_kernel<c64>, dim3((unsigned)blocks), dim3(256), 0, stream, p, fac); break;
+        case 3: hipLaunchKernelGGL(accum_source_maxabs_kernel<c128>, dim3((unsigned)blocks), dim3(256), 0, stream, p, fac); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 // largest |re|, |im| of n complex64 values as a FLOAT: the power-of-two scale of a big operand of the fp16 x 2 stem
 // kernels that no producer recorded (CTG_STEM_H2_ALL=1: tests and diagnostics -- by default such a pair is multiplied in
 // bf16 x 3 instead, ctg_runtime.hip); *out must be zero
@@ -797,6 +845,12 @@ __global__ void strip_prepare_kernel(const double* fac, const int32_t* counted, 
     for (int64_t s = 0; s < n_steps; ++s) {
         if (!counted[s]) continue;
         const double f = fac[s];
+        if (counted[s] == 2) {
+            // (the slice output of a plan without a pair step: check_zero's zero test alone -- nothing is normalised,
+            // and without check_zero no pass has filled the slot)
+            if (check_zero && f == 0.0) zero = true;
+            continue;
+        }
         if (f == 0.0) zero = true;
         e += log10(f);
     }

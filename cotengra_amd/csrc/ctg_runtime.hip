@@ -1251,8 +1251,11 @@ int launch_step(ctg_exec* e, int64_t s, hipStream_t stream) {
         case KIND_SINGLE: err = launch_single(p->dtype, e->args[s], stream); break;
         case KIND_ACCUM:
             if (e->strip) {
-                err = launch_strip_prepare(e->d_fac, e->d_counted, p->n_steps, e->root_step,
-                                           e->check_zero, e->d_strip, e->d_inscale, stream);
+                if (e->check_zero && s == e->zero_probe_step)
+                    err = launch_accum_source_maxabs(p->dtype, e->args[s], e->d_fac + s, stream);
+                if (err == hipSuccess)
+                    err = launch_strip_prepare(e->d_fac, e->d_counted, p->n_steps, e->root_step,
+                                               e->check_zero, e->d_strip, e->d_inscale, stream);
                 if (err == hipSuccess)
                     err = launch_rescale(p->dtype, e->d_result, p->result_elems, e->d_strip, stream);
                 if (err == hipSuccess && e->d_wide)
@@ -2071,6 +2074,22 @@ int ctg_exec_create(const ctg_plan* p, int device, void* stream, void* ext_resul
                 e->root_step = st;  // the last pair step produces the slice output
             }
         }
+        if (e->root_step < 0) {
+            // no pair step (a one-input tree): no factor, no normalisation, the exponent stays where the upload put it
+            // -- but a zero slice is still check_zero's to find.  The plan's one accumulate step is marked 2: its slot
+            // of d_fac takes the largest element of what it adds (launch_step), for the zero test alone
+            int64_t n_acc = 0, acc = -1;
+            for (int64_t st = 0; st < p->n_steps; ++st)
+                if (p->steps[st * STEP_WORDS + W_KIND] == KIND_ACCUM) {
+                    ++n_acc;
+                    acc = st;
+                }
+            if (n_acc == 1) {
+                counted[acc] = 2;
+                fac_zero[acc] = 1;
+                e->zero_probe_step = acc;
+            }
+        }
         {
             // fp16 x 2 stem kernels: per step the largest element it recorded | of its big operand
             bool stems = false;
@@ -2717,7 +2736,8 @@ int ctg_exec_step_kernel(ctg_exec* e, int64_t step, char* buf, int64_t buflen) {
     if (!e->lds_comp_of.empty() && e->lds_comp_of[step] >= 0) {
         snprintf(name, sizeof(name), "lds_run_kernel[%d]", (int)e->lds_comp_of[step]);
     } else if (r[W_KIND] == KIND_SINGLE) {
-        snprintf(name, sizeof(name), "single_kernel");
+        // (for the launch of one slice: the route is a function of the step's K and R alone)
+        single_name(e->args[step], name, sizeof(name));
     } else if (r[W_KIND] == KIND_ACCUM) {
         snprintf(name, sizeof(name), (size_t)step < e->accum_member.size() && e->accum_member[step] ? "accum_group_kernel"
                                                                                                     : "accum_kernel");

@@ -198,7 +198,10 @@ int ctg_exec_zero_result(ctg_exec* exec);
  * and slices are combined with the exponent-aware adder of core.py:125-172.
  * With strip on, the result tensor holds the mantissa and ctg_exec_get_exponent
  * returns the base-10 exponent E (result = mantissa * 10^E; E = -inf and
- * *zero = 1 when check_zero met a zero intermediate in every slice). */
+ * *zero = 1 when check_zero met a zero intermediate in every slice).  A plan
+ * without a pairwise step (a one-input tree) has nothing to normalise: its
+ * exponent is what the upload took out of the input, and check_zero tests the
+ * slice output itself, so an all-zero result is (0, -inf) there too. */
 int ctg_exec_set_strip_exponent(ctg_exec* exec, int strip_exponent, int check_zero);
 
 /* Arithmetic of the fused stem pairs (step kind 3) of this executor.  1 (the default since ABI 4):
@@ -329,6 +332,10 @@ int ctg_exec_profile_slice(ctg_exec* exec, int64_t slice_id, float* ms);
  * below the root (kernel code 3) is
  *   "pair_pick_rows_kernel<float|double|c64|c128,VEC>"       vector form, VEC 1 | 2 adjacent k per load
  *   "pair_pick_rows_mfma_kernel<c64>"                        matrix-core form (row_lo >= 32, N >= 8, K >= 8)
+ * A single-term step (diagonal, trace, sum, transpose, the preprocessing of a leaf) is
+ *   "single_wave_kernel"                                     a wave per output, lanes along the sum (K >= 256, R <= 2^14)
+ *   "single_kernel"                                          a thread per output (everything else)
+ * and the slice sum "accum_kernel" ("accum_group_kernel": gradients sharing a launch).
  * Match by prefix. */
 int ctg_exec_step_kernel(ctg_exec* exec, int64_t step, char* buf, int64_t buflen);
 /* Added to ABI 10 WITHOUT a bump of CTG_ABI_VERSION: one new symbol, nothing else changes.
