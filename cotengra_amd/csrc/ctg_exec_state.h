@@ -227,3 +227,7 @@ __attribute__((visibility("hidden"))) int reduce_reserve(ctg_exec* e, int64_t wa
 // LDS-resident subtrees (ctg_lds_host.hip): descriptor validation (host only) and per-executor packing
 __attribute__((visibility("hidden"))) int ctg_lds_validate(const ctg_plan* p);
 __attribute__((visibility("hidden"))) int ctg_lds_build(ctg_exec* e);
+// the host half of ctg_lds_build on its own -- forms and packing from the plan alone, nothing uploaded (-> a digest)
+__attribute__((visibility("hidden"))) int64_t ctg_lds_host_reads(const ctg_plan* p);
+// (ctg_runtime.hip) every host function executor creation runs over a validated plan's tables, without a device
+extern "C" __attribute__((visibility("hidden"))) int64_t ctg_plan_host_reads_(const ctg_plan* p);

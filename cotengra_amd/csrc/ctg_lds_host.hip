@@ -26,9 +26,19 @@ int lfail(int code, const char* fmt, ...) {
     return code;
 }
 
+// (no sum of the caller's numbers is formed: off = INT64_MAX does not wrap)
 bool in_blob(const ctg_plan* p, int64_t off, int64_t len) {
-    return off >= 0 && len >= 1 && off + len <= (int64_t)p->tables.size();
+    const int64_t n = (int64_t)p->tables.size();
+    return off >= 0 && len >= 1 && len <= n && off <= n - len;
 }
+
+// [off, off + size) inside a buffer of cap elements, size >= 1
+bool in_range(int64_t off, int64_t size, int64_t cap) {
+    return off >= 0 && size >= 1 && size <= cap && off <= cap - size;
+}
+
+// every term of an address is held to [0, kAddrLim] before it is summed (ctg_runtime.hip: the same rule)
+constexpr int64_t kAddrLim = 1ll << 56;
 
 void tab_range(const ctg_plan* p, int64_t off, int64_t len, int64_t* mn, int64_t* mx) {
     *mn = INT64_MAX;
@@ -176,17 +186,21 @@ int ctg_lds_validate(const ctg_plan* p) {
         const int64_t* h = &p->tables[d];
         if (h[LH_MAGIC] != LR_MAGIC || h[LH_ID] != cid) return lfail(CTG_E_INVALID, "LDS component %lld: bad descriptor", cl);
         const int64_t n_rec = h[LH_NREC], elems = h[LH_ELEMS];
-        if (n_rec < 1 || n_rec > 4096 || elems < 0 || elems * isz > LDS_RUN_MAX_BYTES)
+        if (n_rec < 1 || n_rec > 4096 || elems < 0 || elems > LDS_RUN_MAX_BYTES / isz)   // (no product of the caller's number)
             return lfail(CTG_E_INVALID, "LDS component %lld: bad size", cl);
         if (!in_blob(p, d, LR_HEAD_WORDS + n_rec * LR_WORDS))
             return lfail(CTG_E_BOUNDS, "LDS component %lld: records outside the blob", cl);
         int64_t phase = 0, sharing = -1;
         std::vector<int64_t> seen;
+        // per record: its phase, the LDS element range its result occupies and those of all its LDS operands
+        struct Span { int64_t lo, hi; };
+        struct Touch { int64_t phase; Span c; Span all[3]; int n_all; };
+        std::vector<Touch> touch((size_t)n_rec);
         for (int64_t i = 0; i < n_rec; ++i) {
             const int64_t* q = h + LR_HEAD_WORDS + i * LR_WORDS;
             const int64_t kind = q[LR_KIND], main = q[LR_MAIN], gop = q[LR_GOP];
             if (kind != 0 && kind != 1) return lfail(CTG_E_INVALID, "LDS component %lld: bad record kind", cl);
-            if (q[LR_PHASE] < phase || (kind == 0) != (q[LR_PHASE] == 0))
+            if (q[LR_PHASE] < phase || q[LR_PHASE] > (1 << 16) || (kind == 0) != (q[LR_PHASE] == 0))
                 return lfail(CTG_E_INVALID, "LDS component %lld: bad phase order", cl);
             phase = q[LR_PHASE];
             if (main < 0 || main >= p->n_steps || p->steps[main * STEP_WORDS + W_LDS_COMP] != cid + 1)
@@ -197,12 +211,23 @@ int ctg_lds_validate(const ctg_plan* p) {
             const int64_t R = q[LR_R], K = q[LR_K], N = q[LR_N], row_lo = q[LR_ROW_LO], row_hi = q[LR_ROW_HI_LEN],
                           k_lo = q[LR_K_LO], k_hi = q[LR_K_HI_LEN];
             if (R < 1 || K < 1 || N < 1 || row_lo < 1 || row_hi < 1 || k_lo < 1 || k_hi < 1 || R > (1 << 24) ||
-                K > (1 << 16) || N > (1 << 16) || row_lo * row_hi != R || k_lo * k_hi != K)
+                K > (1 << 16) || N > (1 << 16) || row_lo > R || row_hi > R || k_lo > K || k_hi > K ||   // (then no product wraps)
+                row_lo * row_hi != R || k_lo * k_hi != K)
                 return lfail(CTG_E_INVALID, "LDS component %lld: bad extents", cl);
+            // the kernel counts work items and multiply-adds of a record in 32 bits (with R <= 2^24 and K, N <= 2^16
+            // neither product leaves 64 bits here)
+            const int64_t tn = N >= 3 ? 4 : N;
+            if (R * ((N + tn - 1) / tn) > INT32_MAX || R * K * N > INT32_MAX)
+                return lfail(CTG_E_INVALID, "LDS component %lld: record %lld: more work items than 32 bits count", cl, (long long)i);
+            for (int w : {LR_A_LDS, LR_B_LDS, LR_C_LDS})
+                if (q[w] != 0 && q[w] != 1) return lfail(CTG_E_INVALID, "LDS component %lld: bad operand flag", cl);
             if (kind == 0) {
                 if (N != 1 || q[LR_A_LDS] != 0 || q[LR_C_LDS] != 1 || (gop != 0 && gop != 1) ||
                     (gop == 1 && m[W_KIND] != KIND_PAIR))
                     return lfail(CTG_E_INVALID, "LDS component %lld: bad load record", cl);
+                // (a load has no second operand: written as not in LDS, offset 0, no elements)
+                if (q[LR_B_LDS] != 0 || q[LR_B_OFF] != 0 || q[LR_B_SIZE] != 0)
+                    return lfail(CTG_E_INVALID, "LDS component %lld: record %lld: a load names a second operand", cl, (long long)i);
                 if (m[W_KIND] == KIND_SINGLE) seen.push_back(main);
             } else {
                 if (q[LR_A_LDS] != 1 || q[LR_B_LDS] != 1 || m[W_KIND] != KIND_PAIR ||
@@ -210,47 +235,86 @@ int ctg_lds_validate(const ctg_plan* p) {
                     return lfail(CTG_E_INVALID, "LDS component %lld: bad pair record", cl);
                 seen.push_back(main);
             }
-            // operands: tables inside the blob, addresses inside the data area / the global space
-            struct Op { int lds_w, off_w; int64_t rhi, rlo, khi, klo, n; bool used; int main_space, main_off, main_leaf; };
+            // tables: the packer (ctg_lds_pack) indexes every table of the record's kind itself, whatever its length --
+            // none of those may be absent; a table it does not read (B's, and the column tables, of a load) is
+            // absent or points into the blob.  Entries in [0, 2^56].
+            struct Tab { int word, op; int64_t len; bool read; };
+            const bool pr = kind == 1;
+            const Tab tabs[12] = {
+                {LR_ROWA_HI, 0, row_hi, true}, {LR_ROWA_LO, 0, row_lo, true}, {LR_ROWB_HI, 1, row_hi, pr}, {LR_ROWB_LO, 1, row_lo, pr},
+                {LR_ROWC_HI, 2, row_hi, true}, {LR_ROWC_LO, 2, row_lo, true}, {LR_KA_HI, 0, k_hi, true}, {LR_KA_LO, 0, k_lo, true},
+                {LR_KB_HI, 1, k_hi, pr}, {LR_KB_LO, 1, k_lo, pr}, {LR_NB, 1, N, pr}, {LR_NC, 2, N, pr}};
+            int64_t lo_addr[3] = {0, 0, 0}, hi_addr[3] = {0, 0, 0};
+            for (const Tab& t : tabs) {
+                const int64_t w = q[t.word];
+                if (w < 0) {
+                    if (t.read)
+                        return lfail(CTG_E_INVALID, "LDS component %lld: record %lld word %d: a table the packer reads is absent",
+                                     cl, (long long)i, t.word);
+                    continue;
+                }
+                if (!in_blob(p, w, t.read ? t.len : 1))
+                    return lfail(CTG_E_BOUNDS, "LDS component %lld: record %lld word %d: table outside the blob", cl, (long long)i, t.word);
+                if (!t.read) continue;
+                int64_t mn, mx;
+                tab_range(p, w, t.len, &mn, &mx);
+                if (mn < 0 || mx > kAddrLim)
+                    return lfail(CTG_E_BOUNDS, "LDS component %lld: record %lld word %d: negative or oversized offset", cl, (long long)i, t.word);
+                lo_addr[t.op] += mn;
+                hi_addr[t.op] += mx;
+            }
+            // operands: the elements [off, off + size) inside the data area / the global space, every address the
+            // tables form inside them
+            struct Op { int lds_w, off_w, size_w; bool used; int main_space, main_off, main_leaf; };
             const Op ops[3] = {
-                {LR_A_LDS, LR_A_OFF, q[LR_ROWA_HI], q[LR_ROWA_LO], q[LR_KA_HI], q[LR_KA_LO], -1, true,
+                {LR_A_LDS, LR_A_OFF, LR_A_SIZE, true,
                  gop == 1 ? W_B_SPACE : W_A_SPACE, gop == 1 ? W_B_OFF : W_A_OFF, gop == 1 ? W_B_LEAF : W_A_LEAF},
-                {LR_B_LDS, LR_B_OFF, q[LR_ROWB_HI], q[LR_ROWB_LO], q[LR_KB_HI], q[LR_KB_LO], q[LR_NB], kind == 1, 0, 0, 0},
-                {LR_C_LDS, LR_C_OFF, q[LR_ROWC_HI], q[LR_ROWC_LO], -1, -1, kind == 1 ? q[LR_NC] : -1, true,
-                 W_C_SPACE, W_C_OFF, W_C_LEAF},
+                {LR_B_LDS, LR_B_OFF, LR_B_SIZE, kind == 1, 0, 0, 0},
+                {LR_C_LDS, LR_C_OFF, LR_C_SIZE, true, W_C_SPACE, W_C_OFF, W_C_LEAF},
             };
+            Touch& tc = touch[(size_t)i];
+            tc.phase = phase;
+            tc.c = Span{0, -1};
+            tc.n_all = 0;
             for (int o = 0; o < 3; ++o) {
                 const Op& op = ops[o];
                 if (!op.used) continue;
-                int64_t lo_addr = 0, hi_addr = 0;
-                const struct { int64_t t, len; } tabs[5] = {{op.rhi, row_hi}, {op.rlo, row_lo}, {op.khi, k_hi}, {op.klo, k_lo}, {op.n, N}};
-                for (const auto& t : tabs) {
-                    if (t.t < 0) continue;
-                    if (!in_blob(p, t.t, t.len)) return lfail(CTG_E_BOUNDS, "LDS component %lld: table outside the blob", cl);
-                    int64_t mn, mx;
-                    tab_range(p, t.t, t.len, &mn, &mx);
-                    if (mn < 0) return lfail(CTG_E_BOUNDS, "LDS component %lld: negative offset", cl);
-                    lo_addr += mn;
-                    hi_addr += mx;
-                }
-                if (o != 1 && (op.rhi < 0 || op.rlo < 0)) return lfail(CTG_E_INVALID, "LDS component %lld: missing row table", cl);
+                const int64_t size = q[op.size_w];
                 if (q[op.lds_w] == 1) {
                     const int64_t off = q[op.off_w];
-                    if (off < 0 || off + hi_addr >= elems || hi_addr >= 65536)
-                        return lfail(CTG_E_BOUNDS, "LDS component %lld: record %lld operand %c reaches LDS element %lld of %lld",
-                                     cl, (long long)i, "ABC"[o], (long long)(off + hi_addr), (long long)elems);
+                    if (!in_range(off, size, elems) || hi_addr[o] >= size || hi_addr[o] >= 65536)
+                        return lfail(CTG_E_BOUNDS, "LDS component %lld: record %lld operand %c (%lld elements at %lld) reaches LDS element %lld of %lld",
+                                     cl, (long long)i, "ABC"[o], (long long)size, (long long)off, (long long)hi_addr[o], (long long)elems);
+                    const Span sp{off + lo_addr[o], off + hi_addr[o]};
+                    tc.all[tc.n_all++] = sp;
+                    if (o == 2) tc.c = sp;
                 } else {
                     const int64_t space = m[op.main_space], off = m[op.main_off], leaf = m[op.main_leaf];
                     const int64_t cap = space_cap(p, space);
                     if (cap < 0 || leaf < -1 || leaf > p->n_inputs) return lfail(CTG_E_INVALID, "LDS component %lld: bad global operand", cl);
                     if (o == 2 && space == SPACE_INPUTS) return lfail(CTG_E_INVALID, "LDS component %lld: writes into the inputs space", cl);
-                    const int64_t top = off + (leaf >= 0 ? p->max_soff[leaf] : 0) + hi_addr;
-                    if (off < 0 || top >= cap || hi_addr >= (1ll << 31))
-                        return lfail(CTG_E_BOUNDS, "LDS component %lld: record %lld operand %c reaches element %lld of a space of %lld",
-                                     cl, (long long)i, "ABC"[o], (long long)top, (long long)cap);
+                    // (the global side is addressed from the member step's own words: the record's offset word is 0)
+                    if (q[op.off_w] != 0) return lfail(CTG_E_INVALID, "LDS component %lld: record %lld: an LDS offset on a global operand", cl, (long long)i);
+                    const int64_t top = (leaf >= 0 ? p->max_soff[leaf] : 0) + hi_addr[o];
+                    if (!in_range(off, size, cap) || top >= size || hi_addr[o] >= (1ll << 31))
+                        return lfail(CTG_E_BOUNDS, "LDS component %lld: record %lld operand %c (%lld elements at %lld) reaches element %lld of a space of %lld",
+                                     cl, (long long)i, "ABC"[o], (long long)size, (long long)off, (long long)top, (long long)cap);
                 }
             }
         }
+        // Records of one phase run between the same two barriers: none may read or write the LDS range another one's
+        // result is written to
+        for (size_t i = 0; i < touch.size(); ++i)
+            for (size_t j = i + 1; j < touch.size() && touch[j].phase == touch[i].phase; ++j) {
+                auto hits = [](const Span& c, const Touch& t) {
+                    for (int k = 0; k < t.n_all; ++k)
+                        if (c.lo <= t.all[k].hi && t.all[k].lo <= c.hi) return true;
+                    return false;
+                };
+                if (hits(touch[i].c, touch[j]) || hits(touch[j].c, touch[i]))
+                    return lfail(CTG_E_INVALID, "LDS component %lld: records %lld and %lld of phase %lld meet in the LDS range one of them writes",
+                                 cl, (long long)i, (long long)j, (long long)touch[i].phase);
+            }
         // every member is lowered exactly once
         std::sort(seen.begin(), seen.end());
         for (size_t i = 1; i < seen.size(); ++i)
@@ -262,35 +326,36 @@ int ctg_lds_validate(const ctg_plan* p) {
     return CTG_OK;
 }
 
-// Pack the components the executor will run LDS-resident: per component one blob (LdsStepDev records, then
-// tables with 16-bit LDS offsets) in device memory.  A component whose blob + data do not fit the LDS, or
-// whose offsets do not fit their fields, stays off: its members launch one by one as ordinary steps.
-// Fills e->lds_comp_of / lds_first / lds_count / lds_bytes, e->d_lds_comps, e->d_lds_blob.
-int ctg_lds_build(ctg_exec* e) {
-    const ctg_plan* p = e->plan;
+namespace {
+
+// A component as the host half leaves it: the blob its workgroup copies into LDS (LdsStepDev records, then tables with
+// 16-bit LDS offsets), the form of every record, and which operand of its member step is the record's global side (-1:
+// none) -- the device addresses of that side are the upload half's to fill in.
+struct LdsPacked {
+    int64_t cid;
+    std::vector<char> blob;
+    std::vector<LdsForm> forms;
+    std::vector<int64_t> gop;
+    uint32_t n_steps, data_off;
+    int lds_bytes;
+    bool shared;
+};
+
+// The host half of the packing: forms and blobs of the components of a validated plan, from the plan alone -- no device,
+// no executor.  `invariant` (or null): per step, the executor runs it once per upload; a component with such a member
+// stays off.  A component whose blob + data do not fit the LDS, or whose offsets do not fit their fields, stays off
+// too: its members launch one by one as ordinary steps.
+void ctg_lds_pack(const ctg_plan* p, const std::vector<char>* invariant, bool no_mfma, std::vector<LdsPacked>& packed) {
     const int64_t isz = ctg_item_size(p->dtype);
-    e->lds_comp_of.assign(p->n_steps, -1);
-    for (int c = 0; c < 2; ++c) e->lds_first[c] = e->lds_count[c] = e->lds_bytes[c] = 0;
-    if (e->d_lds_comps) (void)hipFree(e->d_lds_comps);
-    if (e->d_lds_blob) (void)hipFree(e->d_lds_blob);
-    e->d_lds_comps = nullptr;
-    e->d_lds_blob = nullptr;
-    e->lds_forms.clear();
-    // (strip_exponent keeps a scale per step: the ordinary steps run)
-    if (e->strip || env_on("CTG_NO_LDS_RUNS")) return CTG_OK;
     std::map<int64_t, int64_t> comp_desc;
     for (int64_t s = 0; s < p->n_steps; ++s) {
         const int64_t* r = &p->steps[s * STEP_WORDS];
         if (r[W_LDS_COMP] > 0) comp_desc[r[W_LDS_COMP] - 1] = r[W_LDS_DESC];
     }
-    if (comp_desc.empty()) return CTG_OK;
-    struct Packed { int64_t cid; std::vector<char> blob; std::vector<LdsForm> forms; uint32_t n_steps, data_off; int lds_bytes; bool shared; };
-    const bool no_mfma = env_on("CTG_LDS_NO_MFMA");
-    std::vector<Packed> packed;
     for (const auto& cd : comp_desc) {
         const int64_t* h = &p->tables[cd.second];
         const int64_t n_rec = h[LH_NREC], elems = h[LH_ELEMS];
-        Packed pk;
+        LdsPacked pk;
         pk.cid = cd.first;
         pk.n_steps = (uint32_t)n_rec;
         std::vector<LdsStepDev> recs((size_t)n_rec);
@@ -312,7 +377,8 @@ int ctg_lds_build(ctg_exec* e) {
             const int64_t main = q[LR_MAIN], gop = q[LR_GOP], kind = q[LR_KIND];
             const int64_t* m = &p->steps[main * STEP_WORDS];
             pk.shared = m[W_INVARIANT] == 2;
-            if (e->invariant[main]) ok = false;
+            if (invariant && (*invariant)[(size_t)main]) ok = false;
+            pk.gop.push_back(gop);
             LdsStepDev& st = recs[(size_t)i];
             memset(&st, 0, sizeof(st));
             st.kind = (int32_t)kind;
@@ -378,13 +444,7 @@ int ctg_lds_build(ctg_exec* e) {
                 }
                 st.t_n = put(ent.data(), ent.size() * 4);
             }
-            // the global side, exactly as the ordinary step addresses it
-            if (gop >= 0) {
-                const StepArgs& a = e->args[main];
-                if (gop == 0) { st.gptr = (const char*)a.A; st.gsoff = a.soffA; st.gz = a.zA; st.gzs = (int32_t)a.zsA; st.gzq = a.zqA; }
-                else if (gop == 1) { st.gptr = (const char*)a.B; st.gsoff = a.soffB; st.gz = a.zB; st.gzs = (int32_t)a.zsB; st.gzq = a.zqB; }
-                else { st.gptr = (const char*)a.C; st.gsoff = a.soffC; st.gz = a.zC; st.gzs = (int32_t)a.zsC; st.gzq = 0; }
-            }
+            // (the global side -- gptr, gsoff, gz, gzs, gzq -- is the upload half's: ctg_lds_build)
         }
         if (!ok) continue;
         // table offsets are relative to the blob: records first
@@ -405,7 +465,53 @@ int ctg_lds_build(ctg_exec* e) {
         pk.lds_bytes = (int)((total + 15) / 16 * 16);
         packed.push_back(std::move(pk));
     }
+}
+
+}  // namespace
+
+// (not part of the ABI) the host half alone, with and without the matrix-core forms: what executor creation reads of a
+// validated plan's LDS descriptors before anything is uploaded (ctg_runtime.hip: ctg_plan_host_reads_)
+int64_t ctg_lds_host_reads(const ctg_plan* p) {
+    int64_t seen = 0;
+    for (const bool no_mfma : {false, true}) {
+        std::vector<LdsPacked> packed;
+        ctg_lds_pack(p, nullptr, no_mfma, packed);
+        for (const LdsPacked& pk : packed) seen += (int64_t)pk.blob.size() + (int64_t)pk.forms.size() + pk.lds_bytes;
+    }
+    return seen;
+}
+
+// Pack the components the executor will run LDS-resident (ctg_lds_pack, the host half) and upload them: per component
+// one blob in device memory, the global side of its records addressed exactly as the member step addresses it.
+// Fills e->lds_comp_of / lds_first / lds_count / lds_bytes, e->d_lds_comps, e->d_lds_blob.
+int ctg_lds_build(ctg_exec* e) {
+    const ctg_plan* p = e->plan;
+    e->lds_comp_of.assign(p->n_steps, -1);
+    for (int c = 0; c < 2; ++c) e->lds_first[c] = e->lds_count[c] = e->lds_bytes[c] = 0;
+    if (e->d_lds_comps) (void)hipFree(e->d_lds_comps);
+    if (e->d_lds_blob) (void)hipFree(e->d_lds_blob);
+    e->d_lds_comps = nullptr;
+    e->d_lds_blob = nullptr;
+    e->lds_forms.clear();
+    // (strip_exponent keeps a scale per step: the ordinary steps run)
+    if (e->strip || env_on("CTG_NO_LDS_RUNS")) return CTG_OK;
+    typedef LdsPacked Packed;
+    std::vector<Packed> packed;
+    ctg_lds_pack(p, &e->invariant, env_on("CTG_LDS_NO_MFMA"), packed);
     if (packed.empty()) return CTG_OK;
+    // the global side of every record, exactly as the ordinary step addresses it (the records open the blob)
+    for (Packed& pk : packed)
+        for (size_t i = 0; i < pk.gop.size(); ++i) {
+            const int64_t gop = pk.gop[i];
+            if (gop < 0) continue;
+            LdsStepDev st;
+            memcpy(&st, pk.blob.data() + i * sizeof(LdsStepDev), sizeof(st));
+            const StepArgs& a = e->args[pk.forms[i].main];
+            if (gop == 0) { st.gptr = (const char*)a.A; st.gsoff = a.soffA; st.gz = a.zA; st.gzs = (int32_t)a.zsA; st.gzq = a.zqA; }
+            else if (gop == 1) { st.gptr = (const char*)a.B; st.gsoff = a.soffB; st.gz = a.zB; st.gzs = (int32_t)a.zsB; st.gzq = a.zqB; }
+            else { st.gptr = (const char*)a.C; st.gsoff = a.soffC; st.gz = a.zC; st.gzs = (int32_t)a.zsC; st.gzq = 0; }
+            memcpy(pk.blob.data() + i * sizeof(LdsStepDev), &st, sizeof(st));
+        }
     // group-shared components first, per-slice ones after
     std::stable_sort(packed.begin(), packed.end(), [](const Packed& a, const Packed& b) { return a.shared > b.shared; });
     size_t total = 0;

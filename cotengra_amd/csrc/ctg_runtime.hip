@@ -54,7 +54,12 @@ int log2_exact(int64_t v) {
 
 namespace {
 
-// max value of a table range [off, off+len)
+// Every number of a descriptor that enters an address sum -- offsets, sizes, slice offsets, table entries -- is held
+// to [0, kAddrLim] BEFORE it is summed: an address is a sum of at most a dozen of them, which then cannot leave 64 bits
+// (no comparison below is reached by a wrapped sum).
+constexpr int64_t kAddrLim = 1ll << 56;
+
+// max value of a table range [off, off+len) (the caller has asked tab_ok)
 int64_t tab_max(const ctg_plan* p, int64_t off, int64_t len, int64_t* mn) {
     int64_t mx = INT64_MIN;
     *mn = INT64_MAX;
@@ -65,8 +70,39 @@ int64_t tab_max(const ctg_plan* p, int64_t off, int64_t len, int64_t* mn) {
     return mx;
 }
 
+// [off, off + len) lies inside the blob (no sum of the caller's numbers is formed: off = INT64_MAX does not wrap)
 bool tab_ok(const ctg_plan* p, int64_t off, int64_t len) {
-    return off >= 0 && len >= 1 && off + len <= (int64_t)p->tables.size();
+    const int64_t n = (int64_t)p->tables.size();
+    return off >= 0 && len >= 1 && len <= n && off <= n - len;
+}
+
+// an offset / size word pair [off, off + size) inside a buffer of cap elements, size >= 1
+bool range_ok(int64_t off, int64_t size, int64_t cap) {
+    return off >= 0 && size >= 1 && size <= cap && off <= cap - size;
+}
+
+// The offset tables of an ordinary step record (kinds 0, 1, 2): the word, the operand whose address the table enters,
+// its length, and whether anything reads it for this (kind, kernel) -- the one statement of it (include/ctg_hip.h,
+// "Words of a step record"; tests/plan_words.py mirrors it).  A table that is read must be present (>= 0) unless its
+// length is 1: the executor points an absent table at one zero word.  `host`: host code of the executor indexes the
+// tables of this record itself (the gather orders of the matrix-core kernels, the vector test of the pick kernels),
+// so a table that is read must be present whatever its length.
+struct StepTab { int word; int op; int64_t len; bool read; };
+constexpr int kStepTabs = 15;
+void step_tables(const int64_t* r, StepTab* t, bool* host) {
+    const int64_t kind = r[W_KIND], kernel = r[W_KERNEL];
+    const bool pair = kind == KIND_PAIR, mfma = pair && kernel == KERNEL_MFMA, acc = kind == KIND_ACCUM;
+    const int64_t rh = r[W_ROW_HI_LEN], rl = r[W_ROW_LO], kh = r[W_K_HI_LEN], kl = r[W_K_LO], N = r[W_N], Bt = r[W_BT];
+    const StepTab all[kStepTabs] = {
+        {W_ROWA_HI, 0, rh, true}, {W_ROWA_LO, 0, rl, true},
+        {W_ROWB_HI, 1, rh, pair && !mfma}, {W_ROWB_LO, 1, rl, pair && !mfma},
+        {W_ROWC_HI, 2, rh, true}, {W_ROWC_LO, 2, rl, true},
+        {W_KA_HI, 0, kh, !acc}, {W_KA, 0, kl, !acc},
+        {W_KB_HI, 1, kh, pair}, {W_KB, 1, kl, pair},
+        {W_NB, 1, N, pair}, {W_NC, 2, N, pair},
+        {W_BA, 0, Bt, mfma}, {W_BB, 1, Bt, mfma}, {W_BC, 2, Bt, mfma}};
+    for (int i = 0; i < kStepTabs; ++i) t[i] = all[i];
+    *host = pair && kernel != KERNEL_VALU;
 }
 
 int64_t space_elems(const ctg_plan* p, int64_t space) {
@@ -90,6 +126,9 @@ int validate_stem(const ctg_plan* p, int64_t s) {
     if (h[SW_MAGIC] != STEM_MAGIC) return fail(CTG_E_INVALID, "step %lld: bad stem descriptor", sl);
     const int64_t K1 = h[SW_K1], N1 = h[SW_N1], K2 = h[SW_K2], N2 = h[SW_N2], nr1 = h[SW_NR1],
                   rows2 = h[SW_ROWS2], n_tiles = h[SW_NTILES], g_lo = h[SW_GLO];
+    // (the kernels take these as 32-bit numbers: nothing is narrowed before it has been held to a range)
+    for (int w : {SW_K1, SW_N1, SW_K2, SW_N2, SW_NR1, SW_ROWS2, SW_NG2, SW_LD2})
+        if (h[w] < 0 || h[w] > (1 << 16)) return fail(CTG_E_INVALID, "step %lld: stem pair shape the kernel does not take", sl);
     StemArgs a{};
     a.K1 = (int)K1; a.N1 = (int)N1; a.K2 = (int)K2; a.N2 = (int)N2; a.nr1 = (int)nr1;
     a.rows2 = (int)rows2; a.ng2 = (int)h[SW_NG2]; a.ld2 = (int)h[SW_LD2];
@@ -117,6 +156,21 @@ int validate_stem(const ctg_plan* p, int64_t s) {
             return fail(CTG_E_BOUNDS, "step %lld: stem table outside the blob", sl);
         mx[t] = tab_max(p, h[SW_TABS + t], len[t], &mn[t]);
         if (mn[t] < 0) return fail(CTG_E_BOUNDS, "step %lld: negative stem offset", sl);
+        if (mx[t] > kAddrLim) return fail(CTG_E_BOUNDS, "step %lld: stem offset beyond every buffer", sl);
+    }
+    // The words of the record that a pair step's kernels would read are not read for a stem step: the extents restate
+    // the descriptor (R rows of the result over all tiles, K and N of the last step, no splits, no batch), the table
+    // words are absent or, as the executor forms an address from them all the same, point into the blob.
+    {
+        int64_t rows_all = 0;
+        if (__builtin_mul_overflow(n_tiles, one ? rows1 : rows2, &rows_all) || r[W_R] != rows_all || r[W_BT] != 1 ||
+            r[W_K] != (one ? K1 : K2) || r[W_N] != (one ? N1 : N2) || r[W_ROW_LO] != 1 || r[W_ROW_HI_LEN] != 1 ||
+            r[W_K_LO] != 1 || r[W_K_HI_LEN] != 1 || r[W_KERNEL] < 0 || r[W_KERNEL] > 3)
+            return fail(CTG_E_INVALID, "step %lld: the record's extents do not restate the stem descriptor", sl);
+        for (int w : {W_ROWA_HI, W_ROWA_LO, W_ROWB_HI, W_ROWB_LO, W_ROWC_HI, W_ROWC_LO, W_KA, W_KB, W_NB, W_NC, W_BA, W_BB,
+                      W_BC, W_KA_HI, W_KB_HI})
+            if (r[w] >= 0 && !tab_ok(p, r[w], 1))
+                return fail(CTG_E_BOUNDS, "step %lld: table outside the blob", sl);
     }
     // the lane part of a gather address is a 32-bit byte offset in the kernel
     if (mx[ST_LANE_A] >= (1ll << 29))
@@ -139,11 +193,14 @@ int validate_stem(const ctg_plan* p, int64_t s) {
     if (h[SW_TRI] != 0 && h[SW_TRI] != 1) return fail(CTG_E_INVALID, "step %lld: bad stem stage count", sl);
     const bool tri = h[SW_TRI] == 1;
     int64_t bm_top = 0;
+    if (!tri)   // (no middle stage: its words are written as zeros)
+        for (int w = SW_KM; w < SW_TABS_M + 3; ++w)
+            if (w != SW_TRI && h[w] != 0) return fail(CTG_E_INVALID, "step %lld: middle-stage words without a middle stage", sl);
     if (tri) {
         // a middle stage: its shape one the kernel is instantiated for, its tables inside the blob,
         // both intermediates inside the LDS region they share
         const int64_t KM = h[SW_KM], NM = h[SW_NM], rowsM = h[SW_ROWSM];
-        if (one || KM < 16 || KM > 128 || NM < 16 || NM > 128 || rowsM < 32 || rowsM > (1 << 16) ||
+        if (one || h[SW_NGM] < 0 || h[SW_NGM] > (1 << 16) || KM < 16 || KM > 128 || NM < 16 || NM > 128 || rowsM < 32 || rowsM > (1 << 16) ||
             h[SW_LDM] != KM + 4 || rows1 * N1 != rowsM * KM || rowsM * NM != rows2 * K2)
             return fail(CTG_E_INVALID, "step %lld: three-step tile shape the kernel does not take", sl);
         a.tri = 1; a.KM = (int)KM; a.NM = (int)NM; a.rowsM = (int)rowsM; a.ngM = (int)h[SW_NGM]; a.ldM = (int)h[SW_LDM];
@@ -157,6 +214,7 @@ int validate_stem(const ctg_plan* p, int64_t s) {
                 return fail(CTG_E_BOUNDS, "step %lld: stem table outside the blob", sl);
             mxm[t] = tab_max(p, h[SW_TABS_M + t], lenm[t], &mnm[t]);
             if (mnm[t] < 0) return fail(CTG_E_BOUNDS, "step %lld: negative stem offset", sl);
+            if (mxm[t] > kAddrLim) return fail(CTG_E_BOUNDS, "step %lld: stem offset beyond every buffer", sl);
         }
         bm_top = mxm[0];
         if (mx[ST_MID_ROW] + mx[ST_MID_COL] >= rowsM * (KM + 4) || mxm[1] + mxm[2] >= rows2 * (K2 + 4))
@@ -164,10 +222,13 @@ int validate_stem(const ctg_plan* p, int64_t s) {
         const int64_t cap = space_elems(p, h[SW_BM_SPACE]);
         if (cap < 0) return fail(CTG_E_INVALID, "step %lld: bad space", sl);
         if (h[SW_BM_LEAF] < -1 || h[SW_BM_LEAF] > p->n_inputs) return fail(CTG_E_INVALID, "step %lld: bad leaf", sl);
-        const int64_t hi = h[SW_BM_OFF] + (h[SW_BM_LEAF] >= 0 ? p->max_soff[h[SW_BM_LEAF]] : 0) + bm_top;
-        if (h[SW_BM_OFF] < 0 || hi >= cap)
-            return fail(CTG_E_BOUNDS, "step %lld: stem operand m reaches element %lld of a space of %lld", sl,
-                        (long long)hi, (long long)cap);
+        if (!range_ok(h[SW_BM_OFF], h[SW_BM_SIZE], cap))
+            return fail(CTG_E_BOUNDS, "step %lld: stem operand m, %lld elements at %lld, leaves its space of %lld", sl,
+                        (long long)h[SW_BM_SIZE], (long long)h[SW_BM_OFF], (long long)cap);
+        const int64_t hi = (h[SW_BM_LEAF] >= 0 ? p->max_soff[h[SW_BM_LEAF]] : 0) + bm_top;
+        if (hi >= h[SW_BM_SIZE])
+            return fail(CTG_E_BOUNDS, "step %lld: stem operand m reaches element %lld of its %lld", sl,
+                        (long long)hi, (long long)h[SW_BM_SIZE]);
     }
     if (!one && !tri && mx[ST_MID_ROW] + mx[ST_MID_COL] >= rows2 * (K2 + 4))
         return fail(CTG_E_BOUNDS, "step %lld: intermediate tile overflows its LDS", sl);
@@ -181,16 +242,25 @@ int validate_stem(const ctg_plan* p, int64_t s) {
          mx[ST_GC_HI] + mx[ST_GC_LO] + mx[ST_OUT_ROW] + mx[ST_OUT_COL], 'C'},
     };
     for (const Op& op : ops) {
-        if (one && op.name == 'b') continue;
+        if (one && op.name == 'b') {
+            // (a single step has no second small operand: written as space 0, offset 0, no leaf, no elements)
+            if (op.space != 0 || op.off != 0 || op.leaf != -1 || op.size != 0)
+                return fail(CTG_E_INVALID, "step %lld: a single stem step names a second small operand", sl);
+            continue;
+        }
         const int64_t cap = space_elems(p, op.space);
         if (cap < 0) return fail(CTG_E_INVALID, "step %lld: bad space", sl);
         if (op.leaf < -1 || op.leaf > p->n_inputs) return fail(CTG_E_INVALID, "step %lld: bad leaf", sl);
         if (op.name == 'C' && op.space == SPACE_INPUTS)
             return fail(CTG_E_INVALID, "step %lld: writes into the inputs space", sl);
-        const int64_t hi = op.off + (op.leaf >= 0 ? p->max_soff[op.leaf] : 0) + op.top;
-        if (op.off < 0 || hi >= cap)
-            return fail(CTG_E_BOUNDS, "step %lld: stem operand %c reaches element %lld of a space of %lld",
-                        sl, op.name, (long long)hi, (long long)cap);
+        // the operand's elements [off, off + size) inside its space, every address the tables form inside them
+        if (!range_ok(op.off, op.size, cap))
+            return fail(CTG_E_BOUNDS, "step %lld: stem operand %c, %lld elements at %lld, leaves its space of %lld",
+                        sl, op.name, (long long)op.size, (long long)op.off, (long long)cap);
+        const int64_t hi = (op.leaf >= 0 ? p->max_soff[op.leaf] : 0) + op.top;
+        if (hi >= op.size)
+            return fail(CTG_E_BOUNDS, "step %lld: stem operand %c reaches element %lld of its %lld",
+                        sl, op.name, (long long)hi, (long long)op.size);
     }
     return CTG_OK;
 }
@@ -225,9 +295,10 @@ bool stem_pair16_ok(const ctg_plan* p, int64_t s) {
 int validate_plan(ctg_plan* p) {
     if (p->dtype < 0 || p->dtype > 3) return fail(CTG_E_INVALID, "bad dtype %d", p->dtype);
     if (p->n_inputs < 1) return fail(CTG_E_INVALID, "plan needs at least one input");
+    if (p->inputs_elems > kAddrLim || p->arena_elems > kAddrLim || p->result_elems > kAddrLim)
+        return fail(CTG_E_INVALID, "a buffer of more than 2^56 elements");
     for (int64_t i = 0; i < p->n_inputs; ++i) {
-        if (p->input_sizes[i] < 1 || p->input_offsets[i] < 0 ||
-            p->input_offsets[i] + p->input_sizes[i] > p->inputs_elems)
+        if (!range_ok(p->input_offsets[i], p->input_sizes[i], p->inputs_elems))
             return fail(CTG_E_BOUNDS, "input %lld does not fit the inputs space", (long long)i);
     }
     // slices
@@ -236,15 +307,27 @@ int validate_plan(ctg_plan* p) {
     for (int64_t j = 0; j < p->n_sliced; ++j) {
         const int64_t d = p->slice_sizes[j], f = p->slice_fixed[j];
         if (d < 1) return fail(CTG_E_INVALID, "bad slice size");
+        if (f < -1) return fail(CTG_E_INVALID, "bad projected value");
         if (f >= 0 && d != 1) return fail(CTG_E_INVALID, "projected index must have size 1");
         // saturate: trees narrowed for tests can have more than 2^63 slices
         p->nslices = (p->nslices > INT64_MAX / d) ? INT64_MAX : p->nslices * d;
         for (int64_t l = 0; l <= p->n_inputs; ++l) {
             const int64_t st = p->slice_strides[l * p->n_sliced + j];
             if (st < 0) return fail(CTG_E_INVALID, "negative slice stride");
-            p->max_soff[l] += st * (f >= 0 ? f : d - 1);
+            // the largest slice offset of a leaf, summed without leaving 64 bits and held to kAddrLim like every
+            // term of an address
+            int64_t term = 0;
+            if (__builtin_mul_overflow(st, f >= 0 ? f : d - 1, &term) || term > kAddrLim ||
+                (p->max_soff[l] += term) > kAddrLim)
+                return fail(CTG_E_BOUNDS, "slice offsets of leaf %lld beyond every buffer", (long long)l);
         }
     }
+    // the slices of a leaf lie inside the leaf, the chunks of the output inside the result -- whether or not a step
+    // names the leaf (the prologue forms every offset)
+    for (int64_t l = 0; l <= p->n_inputs; ++l)
+        if (p->max_soff[l] >= (l < p->n_inputs ? p->input_sizes[l] : p->result_elems))
+            return fail(CTG_E_BOUNDS, "slice offsets of leaf %lld reach element %lld, outside its tensor", (long long)l,
+                        (long long)p->max_soff[l]);
     // slice groups: flags 0 / 1 on sliced indices that are not projected
     bool any_group = false;
     for (int64_t j = 0; j < p->n_sliced; ++j) {
@@ -292,49 +375,70 @@ int validate_plan(ctg_plan* p) {
         const int64_t k_lo = r[W_K_LO], k_hi = r[W_K_HI_LEN];
         if (R < 1 || Bt < 1 || K < 1 || N < 1 || row_lo < 1 || row_hi < 1 || k_lo < 1 || k_hi < 1)
             return fail(CTG_E_INVALID, "step %lld: non-positive extent", (long long)s);
-        if (row_lo * row_hi != R) return fail(CTG_E_INVALID, "step %lld: row split != R", (long long)s);
-        if (k_lo * k_hi != K) return fail(CTG_E_INVALID, "step %lld: k split != K", (long long)s);
+        int64_t prod = 0;
+        if (__builtin_mul_overflow(row_lo, row_hi, &prod) || prod != R)
+            return fail(CTG_E_INVALID, "step %lld: row split != R", (long long)s);
+        if (__builtin_mul_overflow(k_lo, k_hi, &prod) || prod != K)
+            return fail(CTG_E_INVALID, "step %lld: k split != K", (long long)s);
         if (r[W_KERNEL] == KERNEL_MFMA && Bt > 65535)
             return fail(CTG_E_INVALID, "step %lld: MFMA batch too large", (long long)s);
+        // extents no kernel of the step reads are 1: the batch of everything but the matrix-core kernels (it is folded
+        // into the rows), the columns of a single-term and an accumulate step, the contraction of an accumulate step
+        const bool pair = kind == KIND_PAIR;
+        if ((r[W_KERNEL] != KERNEL_MFMA && Bt != 1) || (!pair && N != 1) || (kind == KIND_ACCUM && K != 1))
+            return fail(CTG_E_INVALID, "step %lld: an extent the step does not have is not 1", (long long)s);
 
-        struct Op { int space_w, off_w, leaf_w, size_w; int64_t rhi, rlo, khi, klo, n, b; bool used; };
-        const bool pair = kind == KIND_PAIR, mfma = r[W_KERNEL] == KERNEL_MFMA;
-        Op ops[3] = {
-            {W_A_SPACE, W_A_OFF, W_A_LEAF, W_A_SIZE, r[W_ROWA_HI], r[W_ROWA_LO],
-             kind != KIND_ACCUM ? r[W_KA_HI] : -1, kind != KIND_ACCUM ? r[W_KA] : -1, -1,
-             mfma ? r[W_BA] : -1, true},
-            {W_B_SPACE, W_B_OFF, W_B_LEAF, W_B_SIZE, mfma ? -1 : r[W_ROWB_HI], mfma ? -1 : r[W_ROWB_LO],
-             r[W_KB_HI], r[W_KB], r[W_NB], mfma ? r[W_BB] : -1, pair},
-            {W_C_SPACE, W_C_OFF, W_C_LEAF, W_C_SIZE, r[W_ROWC_HI], r[W_ROWC_LO], -1, -1,
-             pair ? r[W_NC] : -1, mfma ? r[W_BC] : -1, true},
-        };
+        // tables: what is read is present and inside the blob with its whole length, its entries in [0, 2^56]; what
+        // is not read is absent or points into the blob (the executor forms an address from every table word)
+        StepTab tabs[kStepTabs];
+        bool host = false;
+        step_tables(r, tabs, &host);
+        int64_t top[3] = {0, 0, 0};   // per operand: the sum of its tables' largest entries
+        for (const StepTab& t : tabs) {
+            const int64_t w = r[t.word];
+            if (w < 0) {
+                if (t.read && (t.len > 1 || host))
+                    return fail(CTG_E_INVALID, "step %lld: word %d: a table the step reads is absent", (long long)s, t.word);
+                continue;
+            }
+            if (!tab_ok(p, w, t.read ? t.len : 1))
+                return fail(CTG_E_BOUNDS, "step %lld: word %d: table outside the blob", (long long)s, t.word);
+            if (!t.read) continue;
+            int64_t mn;
+            const int64_t mx = tab_max(p, w, t.len, &mn);
+            if (mn < 0 || mx > kAddrLim)
+                return fail(CTG_E_BOUNDS, "step %lld: word %d: table entry %lld outside every buffer", (long long)s, t.word,
+                            (long long)(mn < 0 ? mn : mx));
+            top[t.op] += mx;
+        }
+        // operands: the elements [off, off + size) inside the space, every address the tables form inside them (a
+        // leaf's size is that of the whole tensor its slice offsets move in)
+        struct Op { int space_w, off_w, leaf_w, size_w; bool used; };
+        const Op ops[3] = {{W_A_SPACE, W_A_OFF, W_A_LEAF, W_A_SIZE, true},
+                           {W_B_SPACE, W_B_OFF, W_B_LEAF, W_B_SIZE, pair},
+                           {W_C_SPACE, W_C_OFF, W_C_LEAF, W_C_SIZE, true}};
         for (int o = 0; o < 3; ++o) {
             const Op& op = ops[o];
-            if (!op.used) continue;
-            const int64_t space = r[op.space_w], off = r[op.off_w], leaf = r[op.leaf_w];
+            const int64_t space = r[op.space_w], off = r[op.off_w], leaf = r[op.leaf_w], size = r[op.size_w];
+            if (!op.used) {
+                // (an operand the step does not have: space -1, offset 0, no leaf, no elements)
+                if (space != -1 || off != 0 || leaf != -1 || size != 0)
+                    return fail(CTG_E_INVALID, "step %lld: names an operand %c it does not have", (long long)s, "ABC"[o]);
+                continue;
+            }
             const int64_t cap = space_elems(p, space);
             if (cap < 0) return fail(CTG_E_INVALID, "step %lld: bad space", (long long)s);
             if (leaf < -1 || leaf > p->n_inputs)
                 return fail(CTG_E_INVALID, "step %lld: bad leaf", (long long)s);
             if (o == 2 && space == SPACE_INPUTS)
                 return fail(CTG_E_INVALID, "step %lld: writes into the inputs space", (long long)s);
-            int64_t lo_addr = off, hi_addr = off + (leaf >= 0 ? p->max_soff[leaf] : 0);
-            struct { int64_t t, len; } tabs[6] = {
-                {op.rhi, row_hi}, {op.rlo, row_lo}, {op.khi, k_hi}, {op.klo, k_lo},
-                {op.n, N}, {op.b, Bt}};
-            for (auto& t : tabs) {
-                if (t.t < 0) continue;
-                if (!tab_ok(p, t.t, t.len))
-                    return fail(CTG_E_BOUNDS, "step %lld: table outside the blob", (long long)s);
-                int64_t mn;
-                const int64_t mx = tab_max(p, t.t, t.len, &mn);
-                hi_addr += mx;
-                lo_addr += mn;
-            }
-            if (lo_addr < 0 || hi_addr >= cap)
-                return fail(CTG_E_BOUNDS,
-                            "step %lld: operand %c addresses [%lld, %lld] outside its space of %lld elements",
-                            (long long)s, "ABC"[o], (long long)lo_addr, (long long)hi_addr, (long long)cap);
+            if (!range_ok(off, size, cap))
+                return fail(CTG_E_BOUNDS, "step %lld: operand %c, %lld elements at %lld, leaves its space of %lld elements",
+                            (long long)s, "ABC"[o], (long long)size, (long long)off, (long long)cap);
+            const int64_t hi = (leaf >= 0 ? p->max_soff[leaf] : 0) + top[o];
+            if (hi >= size)
+                return fail(CTG_E_BOUNDS, "step %lld: operand %c addresses reach element %lld of its %lld, outside its space",
+                            (long long)s, "ABC"[o], (long long)hi, (long long)size);
         }
     }
     // (ABI 8) a run of consecutive accumulate steps goes out as one launch (accum_group_kernel): the result
@@ -344,11 +448,14 @@ int validate_plan(ctg_plan* p) {
         std::vector<std::pair<int64_t, int64_t>> ranges;
         for (; j < p->n_steps && p->steps[j * STEP_WORDS + W_KIND] == KIND_ACCUM; ++j) {
             const int64_t* r = &p->steps[j * STEP_WORDS];
+            // (the step loop above has held every term to [0, 2^56] and every table that is present to the blob; an
+            // absent table -- legal at length 1 -- is one zero)
             int64_t lo = r[W_C_OFF], hi = r[W_C_OFF] + (r[W_C_LEAF] >= 0 ? p->max_soff[r[W_C_LEAF]] : 0), mn;
-            hi += tab_max(p, r[W_ROWC_HI], r[W_ROW_HI_LEN], &mn);
-            lo += mn;
-            hi += tab_max(p, r[W_ROWC_LO], r[W_ROW_LO], &mn);
-            lo += mn;
+            for (const auto& t : {std::make_pair(r[W_ROWC_HI], r[W_ROW_HI_LEN]), std::make_pair(r[W_ROWC_LO], r[W_ROW_LO])}) {
+                if (t.first < 0) continue;
+                hi += tab_max(p, t.first, t.second, &mn);
+                lo += mn;
+            }
             ranges.emplace_back(lo, hi);
         }
         if (ranges.size() > 1) {
@@ -371,7 +478,8 @@ int validate_plan(ctg_plan* p) {
         // ctg_exec_run_slices / ctg_exec_run_share must not hand the work to each other for ever)
         int64_t gsize = 1;
         for (int64_t j = 0; j < p->n_sliced; ++j)
-            if (p->slice_group[j] == 1 && p->slice_fixed[j] < 0) gsize *= p->slice_sizes[j];
+            if (p->slice_group[j] == 1 && p->slice_fixed[j] < 0)
+                gsize = gsize > INT64_MAX / p->slice_sizes[j] ? INT64_MAX : gsize * p->slice_sizes[j];   // (saturate, as nslices)
         if (gsize <= 1) p->has_groups = false;
     }
     if (p->has_groups) {
@@ -875,9 +983,55 @@ bool real_vec_ok(const ctg_plan* p, const int64_t* r, int which, bool kfast, int
     return pieces(r[W_NB], r[W_N]) && all_mult(klo_w, k_lo);
 }
 
+// Every host function above that indexes p->tables from a plan alone, called on every step it can be asked about, with
+// every tile shape build_hints_into may ask it with: what executor creation reads of a plan's tables on the host before
+// anything is launched.  Needs no device; tests/cabi_validate_fuzz.cpp runs it under the address sanitizer on every
+// hostile plan ctg_plan_create accepted.  Returns a digest of what was found, so that no call is optimised away.
+int64_t plan_host_reads(const ctg_plan* p) {
+    int64_t seen = 0;
+    std::vector<uint16_t> blob;
+    for (int64_t s = 0; s < p->n_steps; ++s) {
+        const int64_t* r = &p->steps[s * STEP_WORDS];
+        if (r[W_KIND] == KIND_STEM2) seen += stem_pair16_ok(p, s) ? 1 : 0;
+        if (r[W_KIND] != KIND_PAIR) continue;
+        if (r[W_KERNEL] == KERNEL_PICK || r[W_KERNEL] == KERNEL_PICK_ROWS) {
+            seen += pick_vec_ok(p, r) ? 1 : 0;
+            if (r[W_KERNEL] == KERNEL_PICK_ROWS)
+                for (int64_t i = 0; i < r[W_ROW_LO]; ++i) seen += p->tables[r[W_ROWB_LO] + i] == 0 ? 1 : 0;
+        }
+        if (r[W_KERNEL] != KERNEL_MFMA) continue;
+        if (p->dtype != CTG_C64) {
+            for (int w : {W_KA, W_ROWA_LO, W_KB, W_NB}) seen += p->tables[r[w]] & 1;
+            for (int which = 0; which < 2; ++which)
+                for (int kfast = 0; kfast < 2; ++kfast)
+                    for (int64_t V : {2, 4}) seen += real_vec_ok(p, r, which, kfast != 0, V) ? 1 : 0;
+            continue;
+        }
+        seen += kstream_ok(p, r) ? 1 : 0;
+        seen += skinny_ok(p, r) ? 1 : 0;
+        seen += tile_additive(p, r[W_ROWA_LO], r[W_ROW_LO], r[W_R], 32) ? 1 : 0;
+        seen += tile_additive(p, r[W_ROWC_LO], r[W_ROW_LO], r[W_R], 32) ? 1 : 0;
+        if (r[W_N] >= 2) seen += p->tables[r[W_NC] + 1] - p->tables[r[W_NC]] == 1 ? 1 : 0;
+        for (int bn : {16, 32, 64, 128}) {
+            seen += mfma_fast_ok(p, r, bn) ? 1 : 0;
+            size_t oa = 0, ob = 0;
+            int vec = 0;
+            blob.clear();
+            if (bn <= 64) build_mfma_order(p, r, bn, 32, blob, &oa, &ob, &vec);        // the streaming kernel
+            seen += vec;
+            if (bn <= 32) build_mfma_order(p, r, bn, 32, blob, &oa, &ob, &vec, 64);    // the k-streaming kernel
+            build_mfma_order(p, r, bn, MFMA_BM, blob, &oa, &ob, &vec);
+            seen += vec + (int64_t)blob.size();
+        }
+    }
+    return seen;
+}
+
 // zmult: how many slices a launch with these hints carries at most (1, or the
 // executor's batch size); `like`: hints already built for zmult = 1, whose k-splits
 // are kept
+// (KEEP IN STEP with plan_host_reads above: a predicate asked here with a tile shape, or for a dtype, that it is not
+// asked with there is a host read the sanitizer program never sees)
 int build_hints_into(ctg_exec* e, std::vector<MfmaHints>& hints, int64_t zmult,
                      const std::vector<MfmaHints>* like, uint16_t** d_ord_out, char** d_lane_out) {
     const ctg_plan* p = e->plan;
@@ -1792,6 +1946,13 @@ const char* ctg_last_error(void) { return g_err.c_str(); }
 
 // (shared with the host-only sources of the library; not part of the ABI)
 __attribute__((visibility("hidden"))) void ctg_set_error_(const char* msg) { g_err = msg ? msg : ""; }
+
+// (likewise not part of the ABI: what executor creation reads of a validated plan's tables on the host -- the gather
+// orders and vector tests above, the forms and the packing of the LDS components -- without a device; for the
+// stand-alone sanitizer program tests/cabi_validate_fuzz.cpp, which links the library's objects)
+__attribute__((visibility("hidden"))) int64_t ctg_plan_host_reads_(const ctg_plan* p) {
+    return p ? plan_host_reads(p) + ctg_lds_host_reads(p) : 0;
+}
 
 int ctg_plan_create(const ctg_plan_desc* d, ctg_plan** out) {
     if (!d || !out) return fail(CTG_E_INVALID, "null argument");

@@ -112,7 +112,60 @@ enum {
  *                                                      * B[rowB.hi[m] + rowB.lo[i] + kB(k) + nB[n]].
  * ctg_plan_create rejects code 3 on any other kind of record, with Bt != 1, or with a row, k or n table absent
  * (CTG_E_INVALID), and checks the per-row tables like every table.  The step launches alone and carries the slices
- * of a batch in gridDim.y. */
+ * of a batch in gridDim.y.
+ *
+ * Words of a step record -- what ctg_plan_create holds each of them to (the layout is in cotengra_amd/plan.py:
+ * Plan.serialise; tests/plan_words.py states the same word by word, for the stem and LDS descriptors as well, and
+ * tests/test_plan_validation.py attacks every word with the hostile values of its class).  A descriptor is not trusted:
+ * a word that is accepted can be turned into a host or device address without another look.
+ *   enums          word 0 kind 0..3, word 1 kernel 0..3 (1 on pair steps only, 2 and 3 as above), word 42 sharing 0..2,
+ *                  word 44 LDS component id + 1 (0 .. number of steps, a component with a valid descriptor).
+ *   operands       A (words 2-4, 30), B (5-7, 31), C (8-10, 32): space (0 inputs, 1 arena, 2 result; C never 0), element
+ *                  offset, leaf (-1; an input i whose slice offset moves the operand; n_inputs: the result's chunk offset)
+ *                  and size.  [offset, offset + size) lies inside the space, size >= 1, and every address the tables
+ *                  form -- the leaf's largest slice offset plus the largest entry of every table of the operand -- lies
+ *                  inside [0, size): for a leaf, size is that of the whole tensor its slices lie in.  An operand the step
+ *                  does not have (B of kinds 0 and 2) is written as space -1, offset 0, leaf -1, size 0, nothing else.
+ *   extents        R, Bt, K, N (11-14) and the splits row_lo, row_hi_len (15, 16), k_lo, k_hi_len (36, 39): all >= 1,
+ *                  row_lo * row_hi_len = R, k_lo * k_hi_len = K; Bt <= 65535, and Bt = 1 off the matrix-core kernels;
+ *                  N = 1 on kinds 0 and 2, K = 1 on kind 2.  A kind-3 record restates its descriptor: R the rows of the
+ *                  result over all tiles, K and N those of the last step, Bt and the four splits 1.
+ *   tables         word offsets into the blob, lengths in brackets: rowA/B/C_hi (17, 19, 21) [row_hi_len], rowA/B/C_lo
+ *                  (18, 20, 22) [row_lo], kA/kB_hi (37, 38) [k_hi_len], kA/kB_lo (23, 24) [k_lo], nB, nC (25, 26) [N],
+ *                  bA, bB, bC (27-29) [Bt].  Who reads which: every ordinary step the A and C row tables; kinds 0 and 1
+ *                  the kA tables; kind 1 the kB and n tables; kind 1 off the matrix cores (kernels 0, 2, 3) the B row
+ *                  tables; kernel 1 the b tables; a kind-3 record none.  A table that is read lies inside the blob with
+ *                  its whole length, its entries in [0, 2^56], and is present (>= 0) -- except that on the thread-per-
+ *                  output route (kernel 0, on a step of any kind: single-term, pair or accumulate) a table of length 1
+ *                  may be absent (negative): the executor reads one zero word instead.  Kernels 1, 2 and 3 have host
+ *                  code that indexes their tables: nothing they read may be absent.  A table that is not read is absent
+ *                  or points into the blob.
+ *   step indices   a.producer, b.producer (40, 41): a pair or stem step, or anything outside [0, n_steps) -- "no
+ *                  producer", scale factor 1; tolerated by design.
+ *   descriptors    word 43 (kind 3): STEM_WORDS words inside the blob; word 45 (word 44 > 0): the component's header
+ *                  and records inside the blob.  Free on every other record.
+ *   free           macs, elems_rw, node (33-35), reserved (46, 47): read by nothing.
+ * Sums of the caller's numbers are never formed unchecked: every term of an address is held to [0, 2^56] first, slice
+ * offsets (stride x (extent - 1)) are multiplied with an overflow check, and the slices of every leaf lie inside it.
+ * The stem descriptor's tables are never absent, its second small operand (a single step: space 0, offset 0, leaf -1,
+ * size 0) and its middle stage (none: zeros) follow the operand rule; an LDS record's tables are never absent where the
+ * packer reads them (all of a pair record; the A, C and kA tables of a load), its operands lie inside the component's
+ * data area or, on the global side, inside the member step's space, R * ceil(N / 4) and R * K * N fit 32 bits, and
+ * no record reads or writes the LDS range another record of the same phase writes.
+ *
+ * Changed in ABI 10 WITHOUT a bump of CTG_ABI_VERSION (no symbol, no layout and no plan of cotengra_amd/plan.py changes):
+ * ctg_plan_create REFUSES descriptors it used to accept.  Besides the holes that were never meant to pass (a negative
+ * word for a table that is read, size words, the b tables and the B row tables nobody checked, LDS record tables, sums
+ * that wrapped), a caller that writes its own descriptors must know that these are now pinned, so that every word has
+ * exactly one verdict:
+ *   - Bt = 1 on every step that does not run on the matrix cores; N = 1 on single-term and accumulate steps, K = 1 (and
+ *     both k splits 1) on accumulate steps;
+ *   - an operand a record does not have is space -1, offset 0, leaf -1, size 0 (0 / 0 / -1 / 0 for the second small
+ *     operand of a single stem step and for B of an LDS load record, whose LDS flag is 0);
+ *   - the extent words of a kind-3 record restate its descriptor (R, K, N as above; Bt and the four splits 1);
+ *   - the middle-stage words of a stem descriptor without a middle stage (34-38, 40-47) are zeros;
+ *   - size words are >= 1 and [offset, offset + size) lies inside the space; table entries are never negative;
+ *   - slice_fixed is -1 or a projected value >= 0; the largest slice offset of every leaf lies inside the leaf. */
 typedef struct ctg_plan_desc {
     int32_t dtype;                /* CTG_F32 .. CTG_C128 */
     int64_t n_inputs;
