@@ -558,6 +558,132 @@ def energy_gradient(n, gates, paulis, coeffs, fixed=None, optimize="greedy", dty
     return float(res.energy), res.norm, dparams
 
 
+def _circuit_operator_requests(who, n, operators, fixed):
+    """The validation ``operator_expectation`` and ``operator_energy_gradient`` share -- host only: ``(n, fixed,
+    several?, [(qubits, complex128 (2^k, 2^k) matrix), ...])``."""
+    n = int(n)
+    fixed = {int(q): int(b) for q, b in (fixed or {}).items()}
+    for q, b in fixed.items():
+        if q < 0 or q >= n:
+            raise ValueError(f"fixed: qubit {q} outside the {n} qubits.")
+        if b not in (0, 1):
+            raise ValueError(f"fixed: qubit {q} is projected onto {b}; 0 or 1 is expected.")
+
+    def is_request(p):
+        if not (isinstance(p, (tuple, list)) and len(p) == 2):
+            return False
+        try:
+            arr = np.asarray(p[1])
+        except ValueError:
+            return False
+        return arr.dtype.kind in "iufbc" and arr.ndim >= 2
+
+    if is_request(operators):
+        several, reqs = False, [operators]
+    elif isinstance(operators, (list, tuple)):
+        several, reqs = True, list(operators)
+    else:
+        raise ValueError(f"{who}: operators = {operators!r}; a (qubits, matrix) pair or a list of those is expected.")
+    if len(reqs) > 4096:
+        raise ValueError(f"{who}: {len(reqs)} requests; at most 4096 are taken by one call.")
+    out = []
+    for req in reqs:
+        if not is_request(req):
+            raise ValueError(f"{who}: the request {req!r} is no (qubits, matrix) pair with a numeric matrix.")
+        qs = [req[0]] if not hasattr(req[0], "__iter__") else list(req[0])
+        if not qs:
+            raise ValueError(f"{who}: a request names no qubit.")
+        for q in qs:
+            if isinstance(q, bool) or int(q) != q or not 0 <= int(q) < n:
+                raise ValueError(f"{who}: qubit {q!r} outside the {n} qubits.")
+            if int(q) in fixed:
+                raise ValueError(f"{who}: qubit {q} is fixed; an operator acts on open qubits only.")
+        qs = [int(q) for q in qs]
+        if len(set(qs)) != len(qs):
+            raise ValueError(f"{who}: the qubits {qs} repeat.")
+        if len(qs) > 6:
+            raise ValueError(f"{who}: an operator on {len(qs)} qubits; at most 6.")
+        mat = np.asarray(req[1], dtype=np.complex128)
+        d = 1 << len(qs)
+        if mat.shape != (d, d) and mat.shape != (2,) * (2 * len(qs)):
+            raise ValueError(f"{who}: a matrix of shape {mat.shape} on the qubits {qs}; ({d}, {d}) is expected.")
+        if not np.all(np.isfinite(mat)):
+            raise ValueError(f"{who}: the matrix on the qubits {qs} has an entry that is not finite.")
+        out.append((qs, mat.reshape(d, d)))
+    return n, fixed, several, out
+
+
+def operator_expectation(n, gates, operators, fixed=None, optimize="greedy", dtype="complex64", target_size=None):
+    """Expectation values of dense few-qubit operators in the output state of the ``n``-qubit circuit ``gates``:
+    projectors, number operators, hopping terms, any observable on up to 6 qubits -- without an expansion into Pauli
+    strings.  ``operators``: a list of ``(qubits, matrix)`` pairs (or one pair); ``matrix`` is ``2^k x 2^k``, rows and
+    columns row-major over ``qubits`` in the order given.  ``fixed``: as for :func:`pauli_expectation`; a fixed qubit
+    may not be named.  The values come from reduced density matrices formed on the device
+    (``ContractionTree.contract_operator_expectation``).
+
+    Returns ``(values, norm)``: ``values`` = ``<psi| O |psi> / norm`` per request (a complex128 array; a 0-d complex
+    for one request) and ``norm`` = ``sum |amplitude|^2`` of the open qubits.  ``ValueError`` -- before any device
+    work -- for a qubit outside the circuit, repeated or fixed, more than 6 qubits, a matrix of the wrong shape or
+    with an entry that is not finite, a fixed value other than 0 / 1 and more than 4096 requests; and for a state of
+    norm zero."""
+    from .interface import array_contract_tree
+
+    n, fixed, several, reqs = _circuit_operator_requests("operator_expectation", n, operators, fixed)
+    template = "".join(str(fixed[q]) if q in fixed else "?" for q in range(n))
+    open_qubits = [q for q in range(n) if q not in fixed]
+    inputs, output, size_dict, arrays = circuit_to_network(n, gates, template, simplify=True, dtype=dtype)
+    tree = array_contract_tree(inputs, output, size_dict, optimize=optimize)
+    if [tuple(t) for t in tree.inputs] != [tuple(t) for t in inputs] or tuple(tree.output) != tuple(output):
+        raise ValueError("optimize: the tree is not over this circuit's network.")
+    if target_size is not None:
+        tree = tree.slice(target_size=target_size)
+    label = dict(zip(open_qubits, output))   # (one output index per open qubit, in qubit order)
+    res = tree.contract_operator_expectation(arrays, [([label[q] for q in qs], mat) for qs, mat in reqs])
+    if not res.norm > 0:
+        raise ValueError("operator_expectation: the state has norm zero.")
+    values = np.asarray(res.values, dtype=np.complex128) / res.norm
+    return (values if several else np.complex128(values[0]), res.norm)
+
+
+def operator_energy_gradient(n, gates, operators, fixed=None, optimize="greedy", dtype="complex64", target_size=None,
+                             normalize=True):
+    """Energy ``sum_k <psi| O_k |psi>`` of Hermitian dense few-qubit operators in the output state of the ``n``-qubit
+    circuit ``gates`` and its derivative by every gate parameter, in one step on the device: :func:`energy_gradient`
+    for a Hamiltonian given as matrices.  ``operators``, ``fixed``: as for :func:`operator_expectation`.  Goes through
+    ``ContractionTree.contract_operator_energy``; ``normalize`` as for
+    :func:`energy_gradient`.
+
+    Returns ``(energy, norm, dparams)`` exactly as :func:`energy_gradient` does.  ``ValueError`` -- before any device
+    work -- for what :func:`operator_expectation` refuses and for a matrix that is not Hermitian; and for a state of
+    norm zero under ``normalize``."""
+    from .interface import array_contract_tree
+
+    n, fixed, several, reqs = _circuit_operator_requests("operator_energy_gradient", n, operators, fixed)
+    for qs, mat in reqs:
+        if np.abs(mat - mat.conj().T).max() > 1e-12 * np.abs(mat).max():
+            raise ValueError(f"operator_energy_gradient: the matrix on the qubits {qs} is not Hermitian.")
+    gates = list(gates)
+    derivs = [gate_derivatives(name, params) for name, _, params in gates]
+    template = "".join(str(fixed[q]) if q in fixed else "?" for q in range(n))
+    open_qubits = [q for q in range(n) if q not in fixed]
+    inputs, output, size_dict, arrays = circuit_to_network(n, gates, template, simplify=False, dtype=dtype)
+    tree = array_contract_tree(inputs, output, size_dict, optimize=optimize)
+    if [tuple(t) for t in tree.inputs] != [tuple(t) for t in inputs] or tuple(tree.output) != tuple(output):
+        raise ValueError("optimize: the tree is not over this circuit's network.")
+    if target_size is not None:
+        tree = tree.slice(target_size=target_size)
+    label = dict(zip(open_qubits, output))   # (one output index per open qubit, in qubit order)
+    wrt = [n + k for k, d in enumerate(derivs) if d]
+    res = tree.contract_operator_energy(arrays, [([label[q] for q in qs], mat) for qs, mat in reqs], wrt=wrt,
+                                        normalize=normalize)
+    dparams = []
+    for k, ds in enumerate(derivs):
+        g = None if not ds else np.asarray(res.grads[n + k], dtype=np.complex128).reshape(-1)
+        # dE = Re sum conj(dE / d Re U + i dE / d Im U) dU
+        dparams.append(np.array([float(np.real(np.vdot(g, d.reshape(-1)))) for d in ds], dtype=np.float64))
+    return float(res.energy), res.norm, dparams
+
+
 def _spectrum(rho):
     """Eigenvalues of the trace-normalised Hermitian matrix ``rho``, those below 0 from rounding clipped."""
     rho = np.asarray(rho)

@@ -444,6 +444,110 @@ def pauli_requests(tree, paulis):
     return several, ops
 
 
+def operator_requests(tree, operators):
+    """``operators`` of ``HipContractor.apply_operators`` as ``(several?, canon, terms)`` -- host only.  A request is
+    ``(labels, matrix)``: ``labels`` a sequence of distinct output index labels of any extent ``d_1 .. d_k`` (one
+    label alone may be given bare), ``matrix`` of shape ``(D, D)`` with ``D = d_1 ... d_k`` or ``(d_1 .. d_k, d_1 ..
+    d_k)``, rows and columns row-major over the labels in the order named.  ``operators`` is one request or a list of
+    requests.  ``canon`` holds per request ``(axes, matrix)`` with ``axes`` the ascending positions of its labels in
+    ``tree.output`` and ``matrix`` the complex128 ``(D, D)`` matrix permuted to that order; ``terms`` the same with
+    the requests on one axis set summed (complex128, in the caller's order) into one term, in order of first
+    appearance: what ``ctg_exec_result_op_apply`` takes, each axis set once.  ``ValueError`` for an unknown or
+    repeated label, a label that is not an output index, no label, a matrix of another shape, an entry that is not
+    finite, ``D`` above ``Executor.OP_MAX_DIM``, more than ``Executor.OP_MAX_TERMS`` terms and more than
+    ``Executor.OP_MAX_ENTRIES`` matrix entries in all."""
+    output = list(tree.output)
+    shape = tuple(int(d) for d in tree.gathered_shape())
+
+    def as_matrix(m):
+        if _is_torch(m):
+            m = m.detach().cpu().numpy()
+        try:
+            arr = np.asarray(m)
+        except ValueError:
+            return None
+        return arr if arr.dtype.kind in "iufbc" and arr.ndim >= 2 else None
+
+    def is_request(p):
+        return isinstance(p, (tuple, list)) and len(p) == 2 and as_matrix(p[1]) is not None
+
+    if is_request(operators):
+        several, reqs = False, [operators]
+    elif isinstance(operators, (list, tuple)):
+        several, reqs = True, list(operators)
+    else:
+        raise ValueError(f"operators = {operators!r}: give a (labels, matrix) pair or a list of such pairs.")
+    canon, merged = [], {}
+    for req in reqs:
+        if not is_request(req):
+            raise ValueError(f"operators: the request {req!r} is no (labels, matrix) pair with a numeric matrix.")
+        labels, mat = req[0], as_matrix(req[1])
+        labels = [labels] if isinstance(labels, (str, bytes)) or not hasattr(labels, "__iter__") else list(labels)
+        if not labels:
+            raise ValueError("operators: a request names no label.")
+        pos = []
+        for ix in labels:
+            if ix not in output:
+                raise ValueError(f"operators: {ix!r} is not an output index of the tree (output: {output}).")
+            if output.index(ix) in pos:
+                raise ValueError(f"operators: the label {ix!r} is named twice in one request.")
+            pos.append(output.index(ix))
+        dims = tuple(shape[a] for a in pos)
+        D = prod(dims)
+        if D > runtime.Executor.OP_MAX_DIM:
+            raise ValueError(f"operators: the extents {dims} of {labels} multiply to {D}; at most "
+                             f"{runtime.Executor.OP_MAX_DIM} are taken by one request.")
+        if mat.shape != (D, D) and mat.shape != dims + dims:
+            raise ValueError(f"operators: a matrix of shape {mat.shape} on {labels}; ({D}, {D}) or {dims + dims} is expected.")
+        mat = np.asarray(mat, dtype=np.complex128)
+        if not np.all(np.isfinite(mat)):
+            raise ValueError(f"operators: the matrix on {labels} has an entry that is not finite.")
+        # rows and columns from the caller's order of the labels to ascending axis position
+        k = len(pos)
+        order = tuple(sorted(range(k), key=lambda i: pos[i]))
+        mat = mat.reshape(dims + dims).transpose(order + tuple(k + i for i in order)).reshape(D, D)
+        axes = tuple(pos[i] for i in order)
+        mat = np.array(mat, order="C")
+        canon.append((axes, mat))
+        merged[axes] = merged[axes] + mat if axes in merged else mat.copy()
+    if len(merged) > runtime.Executor.OP_MAX_TERMS:
+        raise ValueError(f"operators: {len(merged)} distinct axis sets; at most {runtime.Executor.OP_MAX_TERMS} are taken by one call.")
+    if sum(m.size for m in merged.values()) > runtime.Executor.OP_MAX_ENTRIES:
+        raise ValueError(f"operators: more than {runtime.Executor.OP_MAX_ENTRIES} matrix entries in all.")
+    return several, canon, list(merged.items())
+
+
+_OperatorEnergyFunction = None
+
+
+def _operator_energy_function():
+    """The ``torch.autograd.Function`` of ``HipContractor.operator_energy_autograd`` (built on first use): the pattern
+    of :func:`_energy_function` with :meth:`HipContractor._operator_energy_forward` as the forward."""
+    global _OperatorEnergyFunction
+    if _OperatorEnergyFunction is not None:
+        return _OperatorEnergyFunction
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class OperatorEnergyFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fn, canon, terms, normalize, box, *arrays):
+            ctx.fn = fn
+            ctx.arrays = [x.detach() if _is_torch(x) else x for x in arrays]
+            energy, box["values"], box["norm"], ctx.y = fn._operator_energy_forward(ctx.arrays, canon, terms, normalize)
+            return torch.tensor(energy, dtype=torch.float64, device=ctx.y.device)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_output):
+            wrt = tuple(i for i, need in enumerate(ctx.needs_input_grad[5:]) if need)
+            grads = ctx.fn._energy_grads(ctx.arrays, ctx.y, wrt, scale=grad_output.real) if wrt else [None] * len(ctx.arrays)
+            return (None,) * 5 + tuple(grads)
+
+    _OperatorEnergyFunction = OperatorEnergyFunction
+    return OperatorEnergyFunction
+
+
 class ExpectationResult(collections.namedtuple("ExpectationResult", "values norm exponent")):
     """What ``HipContractor.expectation`` returns: ``values`` the float64 array of ``<x| P |x> = sum over j of
     conj(x[j]) (P x)[j]`` per requested Pauli string, in the caller's order and NOT normalised (a 0-d float for a
@@ -1316,6 +1420,170 @@ class HipContractor:
         energy = _energy_function().apply(self, ops, c, bool(normalize), box, *arrays)
         values = box["values"]
         return EnergyResult(energy=energy, values=values if several else np.float64(values[0]), norm=box["norm"], grads=None)
+
+    # ---- dense local operators on the result: apply, expectation, energy ------------------- #
+
+    def apply_operators(self, *arrays, operators, strip_exponent=False, check_zero=False, reuse=False):
+        """Contract (all slices, as a call does) and return ``y = (sum over requests of O (x) 1) x`` of the result
+        ``x`` for the dense matrices ``operators`` on named output indices of any extent
+        (:func:`operator_requests`) -- formed on the device next to ``x``, which is not written
+        (``ctg_exec_result_op_apply``).  ``y`` has the result's shape: numpy for numpy inputs,
+        a tensor on the device for ROCm torch inputs.  Returns an :class:`ApplyResult`.  ``ValueError`` -- before
+        the device is touched -- for what :func:`operator_requests` refuses and, in a real contraction, a matrix
+        with an imaginary part.  ``reuse=True``: as for :meth:`topk`; the result stays reusable."""
+        several, canon, terms = operator_requests(self.tree, operators)
+        if reuse and arrays:
+            raise ValueError("reuse=True reads the result of the call before: give no arrays.")
+        shape = tuple(int(d) for d in self.tree.gathered_shape())
+        if arrays:
+            runtime.op_apply_terms(_result_dtype(arrays), shape, terms)   # (a complex matrix in a real contraction)
+        with self._lock:
+            st, strip = self._reduce_state(arrays, strip_exponent, check_zero, reuse)
+            ex = st["exec"]
+            y = self._op_apply_on(st, shape, terms)
+            norm = ex.sample_info()[0] if terms else ex.result_stats()[0]
+            exponent = ex.get_exponent()[0] if strip else 0.0
+        return ApplyResult(y=y, norm=norm, exponent=exponent)
+
+    @staticmethod
+    def _op_apply_on(st, shape, terms):
+        """``y`` of ``Executor.op_apply_result`` for the executor state ``st``: a tensor next to a torch-owned
+        result (``dev_out``), numpy otherwise (``host_out``)."""
+        ex = st["exec"]
+        if "result" in st:
+            import torch
+
+            y = torch.empty(shape, dtype=st["result"].dtype, device=st["result"].device)
+            ex.op_apply_result(shape, terms, out_ptr=y.data_ptr())
+            return y
+        return ex.op_apply_result(shape, terms)
+
+    @staticmethod
+    def _operator_values(ex, shape, canon):
+        """``<x| O |x> = sum over a, b of O[a, b] rho[b, a]`` per request of ``canon``: one ``rdm_result`` per distinct
+        axis set, the trace on the host row after row (a fixed order).  complex128, NOT normalised."""
+        rhos, values = {}, np.zeros(len(canon), dtype=np.complex128)
+        for r, (axes, mat) in enumerate(canon):
+            if axes not in rhos:
+                rhos[axes] = ex.rdm_result(shape, [1 if a in axes else 0 for a in range(len(shape))])
+            rho = rhos[axes]
+            v = 0.0 + 0.0j
+            for a in range(mat.shape[0]):
+                v += complex(np.dot(mat[a, :], rho[:, a]))
+            values[r] = v
+        return values
+
+    def operator_expectation(self, *arrays, operators, strip_exponent=False, check_zero=False, reuse=False):
+        """Contract (all slices, as a call does) and return ``<x| O |x>`` of the result for the dense matrices
+        ``operators`` on named output indices of any extent (:func:`operator_requests`): ``sum over a, b of O[a, b]
+        rho[b, a]`` with ``rho`` the exact fp64 reduced density matrix of the request's indices from the device
+        (``ctg_exec_result_rdm``, one per distinct set of indices of the call) and the trace on the host in a fixed
+        order; the result tensor is never copied to the host.  ``values`` is complex128 (real up to rounding for a
+        Hermitian matrix), one per request, NOT normalised: divide by ``norm``.  Returns an
+        :class:`ExpectationResult`.  ``ValueError`` -- before the device is touched -- for what
+        :func:`operator_requests` refuses.  ``reuse=True``: as for :meth:`topk`.  Not differentiable."""
+        several, canon, terms = operator_requests(self.tree, operators)
+        if reuse and arrays:
+            raise ValueError("reuse=True reads the result of the call before: give no arrays.")
+        shape = tuple(int(d) for d in self.tree.gathered_shape())
+        with self._lock:
+            st, strip = self._reduce_state(arrays, strip_exponent, check_zero, reuse)
+            ex = st["exec"]
+            values = self._operator_values(ex, shape, canon)
+            norm = ex.sample_info()[0] if len(values) else ex.result_stats()[0]
+            exponent = ex.get_exponent()[0] if strip else 0.0
+        return ExpectationResult(values=values if several else np.complex128(values[0]), norm=norm, exponent=exponent)
+
+    def _operator_energy_requests(self, operators, normalize):
+        """``(several?, canon, terms)`` of an operator-energy request, every matrix replaced by its Hermitian part
+        -- host only.  ``ValueError`` under ``strip_exponent``, for what :func:`operator_requests` refuses, for a
+        request that is not Hermitian (``max |O - O^H| > 1e-12 max |O|``) and for ``normalize`` when the identity
+        term of ``(H - (E / N) 1) / N`` -- a one-axis term on axis 0 -- finds no room."""
+        if self.strip_exponent:
+            raise ValueError("operator_energy does not support strip_exponent.")
+        several, canon, _ = operator_requests(self.tree, operators)
+        herm, merged = [], {}
+        for axes, mat in canon:
+            dev = np.abs(mat - mat.conj().T).max()
+            if dev > 1e-12 * np.abs(mat).max():
+                raise ValueError(f"operator_energy: the matrix on the output axes {axes} is not Hermitian: max |O - O^H| = {dev:.3g}.")
+            h = 0.5 * (mat + mat.conj().T)
+            herm.append((axes, h))
+            merged[axes] = merged[axes] + h if axes in merged else h.copy()
+        if normalize and canon:
+            shape = tuple(int(d) for d in self.tree.gathered_shape())
+            if shape[0] > runtime.Executor.OP_MAX_DIM:
+                raise ValueError(f"operator_energy: normalize=True puts its identity term on output axis 0, whose extent {shape[0]} "
+                                 f"exceeds {runtime.Executor.OP_MAX_DIM}.")
+            if (0,) not in merged and len(merged) >= runtime.Executor.OP_MAX_TERMS:
+                raise ValueError(f"operator_energy: normalize=True adds a term to the {len(merged)} of the call; at most "
+                                 f"{runtime.Executor.OP_MAX_TERMS} are taken.")
+        return several, herm, list(merged.items())
+
+    def _operator_energy_forward(self, arrays, canon, terms, normalize):
+        """One contraction, the values of the requests and ``y`` with ``dE = 2 Re <y| dx>``: ``(energy, values, norm,
+        y)``; ``y`` has the result's shape and dtype."""
+        shape = tuple(int(d) for d in self.tree.gathered_shape())
+        real = np.dtype(_result_dtype(arrays)).kind != "c"
+        with self._lock:
+            st, _ = self._reduce_state(arrays, False, False, False)
+            ex = st["exec"]
+            values = self._operator_values(ex, shape, canon)
+            norm = ex.sample_info()[0] if len(values) else ex.result_stats()[0]
+            energy = 0.0
+            for v in values.tolist():
+                energy += v.real
+            use = [(axes, mat) for axes, mat in terms]
+            if real:
+                # (x^T O x of a real x sees the real symmetric part of a Hermitian O alone: so does the gradient)
+                use = [(axes, np.array(mat.real, dtype=np.complex128)) for axes, mat in use]
+            if normalize:
+                if not norm > 0:
+                    raise ValueError("operator_energy: normalize=True and the result has norm zero.")
+                energy = energy / norm
+                # d (E / N) = 2 Re <(H - (E / N) 1) x / N | dx>; the identity as a multiple of the unit matrix on axis 0
+                use = [(axes, mat / norm) for axes, mat in use]
+                if use:
+                    ident = (-energy / norm) * np.eye(shape[0], dtype=np.complex128)
+                    at = [i for i, (axes, _) in enumerate(use) if axes == (0,)]
+                    if at:
+                        use[at[0]] = ((0,), use[at[0]][1] + ident)
+                    else:
+                        use.append(((0,), ident))
+            y = self._op_apply_on(st, shape, use)
+        return energy, values, norm, y
+
+    def operator_energy(self, *arrays, operators, wrt=None, normalize=False):
+        """Energy and gradient in one step on the device for a Hamiltonian of dense local terms on output indices of
+        any extent: ``E = sum over requests of Re <x| O |x>`` of the result ``x`` and ``dE / d(every leaf)``
+        (DESIGN.md section 19).  One contraction; the values as :meth:`operator_expectation` forms them; ``energy``
+        their real parts summed in the caller's order -- divided by ``norm`` under ``normalize``; one
+        ``ctg_exec_result_op_apply`` call forms ``y = H x`` (``(H - (E / N) 1) x / N`` under ``normalize``, the
+        identity folded into a one-axis term on axis 0) in a device buffer; one VJP run with the cotangent ``conj(2
+        y)`` gives the gradients, as for :meth:`energy`.  Every request must be Hermitian (``max |O - O^H| <= 1e-12
+        max |O|``); its Hermitian part is used.  Returns an :class:`EnergyResult` (``values`` complex128).
+        ``ValueError`` -- before the device is touched -- for what :func:`operator_requests` refuses, a request that
+        is not Hermitian and under ``strip_exponent``; ``IndexError`` for ``wrt`` outside the leaves; ``ValueError``
+        for ``normalize`` with norm zero."""
+        several, canon, terms = self._operator_energy_requests(operators, normalize)
+        N = self.tree.N
+        wrt = tuple(range(N)) if wrt is None else tuple(sorted(set(int(i) for i in wrt)))
+        if wrt and (wrt[0] < 0 or wrt[-1] >= N):
+            raise IndexError(f"wrt {wrt} outside the {N} leaves")
+        with self._lock:
+            energy, values, norm, y = self._operator_energy_forward(arrays, canon, terms, normalize)
+            grads = self._energy_grads(arrays, y, wrt) if wrt else [None] * N
+        return EnergyResult(energy=energy, values=values if several else np.complex128(values[0]), norm=norm, grads=grads)
+
+    def operator_energy_autograd(self, *arrays, operators, normalize=False):
+        """:meth:`operator_energy` under torch autograd: ``energy`` is a 0-d float64 tensor on the device with a
+        ``grad_fn`` (the same bits as without autograd) and ``grads`` is ``None``; the forward saves ``y``, the
+        backward runs the one VJP plan for the inputs autograd asks for."""
+        several, canon, terms = self._operator_energy_requests(operators, normalize)
+        box = {}
+        energy = _operator_energy_function().apply(self, canon, terms, bool(normalize), box, *arrays)
+        values = box["values"]
+        return EnergyResult(energy=energy, values=values if several else np.complex128(values[0]), norm=box["norm"], grads=None)
 
     def profile(self, arrays, slice_id=0):
         """Per-step milliseconds for one slice (see ``Plan.describe_steps``)."""

@@ -269,6 +269,35 @@ class ContractExpression:
         self._after_reduce()
         return out
 
+    def apply_operators(self, *arrays, operators, **kwargs):
+        """``expr(*arrays)`` followed by ``y = (sum over requests of O (x) 1) x`` of the result for the dense
+        matrices ``operators`` on named output indices of any extent (``HipContractor.apply_operators``, DESIGN.md
+        section 19); the expression's own ``strip_exponent`` / ``check_zero`` unless given."""
+        kwargs.setdefault("strip_exponent", self.fn.strip_exponent)
+        kwargs.setdefault("check_zero", self.fn.check_zero)
+        out = self.fn.apply_operators(*arrays, operators=operators, **kwargs)
+        self._after_reduce()
+        return out
+
+    def operator_expectation(self, *arrays, operators, **kwargs):
+        """``expr(*arrays)`` followed by ``<x| O |x>`` of the result for the dense matrices ``operators`` on named
+        output indices of any extent (``HipContractor.operator_expectation``); the expression's own
+        ``strip_exponent`` / ``check_zero`` unless given."""
+        kwargs.setdefault("strip_exponent", self.fn.strip_exponent)
+        kwargs.setdefault("check_zero", self.fn.check_zero)
+        out = self.fn.operator_expectation(*arrays, operators=operators, **kwargs)
+        self._after_reduce()
+        return out
+
+    def operator_energy(self, *arrays, operators, wrt=None, normalize=False):
+        """``expr(*arrays)`` followed by the energy of the Hermitian dense matrices ``operators`` on named output
+        indices of any extent and its gradient by the arrays ``wrt`` (default: all) on the device
+        (``HipContractor.operator_energy``); refused by an expression built with
+        ``strip_exponent``."""
+        out = self.fn.operator_energy(*arrays, operators=operators, wrt=wrt, normalize=normalize)
+        self._after_reduce()
+        return out
+
     def device_bytes(self):
         """Device memory this expression's executors hold right now (``ctg_exec_device_bytes``:
         arena x slice batch, inputs, tables, result, scratch), read under the contractor's lock

@@ -7,6 +7,7 @@ raises immediately -- there is no CPU fallback anywhere in the package.
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import os
 
 import numpy as np
@@ -57,6 +58,7 @@ SYMBOLS = (
     "ctg_exec_result_rdm",
     "ctg_exec_result_pauli",
     "ctg_exec_result_pauli_apply",
+    "ctg_exec_result_op_apply",
     "ctg_exec_download_result",
     "ctg_exec_download_arena",
     "ctg_exec_get_state",
@@ -179,6 +181,8 @@ def load():
         "ctg_exec_result_rdm": [vp, C.c_int64, i64p, C.POINTER(C.c_int32), vp],
         "ctg_exec_result_pauli": [vp, C.c_int64, i64p, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_double)],
         "ctg_exec_result_pauli_apply": [vp, C.c_int64, i64p, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_double), vp, vp],
+        "ctg_exec_result_op_apply": [vp, C.c_int64, i64p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_double), vp, vp],
         "ctg_exec_download_result": [vp, vp],
         "ctg_exec_download_arena": [vp, C.c_int64, C.c_int64, vp],
         "ctg_exec_get_state": [vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_int)],
@@ -383,6 +387,85 @@ def pauli_apply_variant(dtype, extents, ops):
     if arr.shape[0] == 0:
         return "none"
     return f"pauli_apply_kernel<{t}>" if _pauli_fast(ext, n) else f"pauli_apply_general_kernel<{t}>"
+
+
+OP_MAX_DIM = 64            # CTG_OP_MAX_DIM
+OP_MAX_TERMS = 4096        # CTG_OP_MAX_TERMS
+OP_MAX_ENTRIES = 1 << 20   # CTG_OP_MAX_ENTRIES
+
+
+def op_apply_terms(dtype, extents, terms):
+    """The terms of a dense-operator request, checked and packed as ``ctg_exec_result_op_apply`` takes them -- host
+    only.  ``terms``: a sequence of ``(axes, matrix)``; ``axes`` distinct positions in ``extents`` in ascending order,
+    ``matrix`` of shape ``(D, D)`` with ``D`` the product of those extents, rows and columns row-major over the axes.
+    Returns ``(extents as ints, naxes int32 (m,), axes int32 (sum naxes,), mats float64 (sum D^2, 2))``.  ``ValueError``
+    -- before any device work -- for everything the C call would refuse: an extent below 1, more than
+    ``OP_MAX_TERMS`` terms, a term without axes, an axis out of range, repeated or not ascending, ``D`` above
+    ``OP_MAX_DIM``, a matrix of another shape, more than ``OP_MAX_ENTRIES`` entries in all, an entry that is not
+    finite and, for a real ``dtype``, a non-zero imaginary part."""
+    ext = [int(v) for v in extents]
+    for v in ext:
+        if v < 1:
+            raise ValueError(f"extent {v} is not positive.")
+    real = np.dtype(dtype).kind != "c"
+    terms = list(terms)
+    if len(terms) > OP_MAX_TERMS:
+        raise ValueError(f"op_apply: {len(terms)} terms; at most {OP_MAX_TERMS} (CTG_OP_MAX_TERMS) per call.")
+    naxes, axes, mats, entries = [], [], [], 0
+    for t, term in enumerate(terms):
+        try:
+            if not isinstance(term, (tuple, list)):
+                raise TypeError
+            ax, mat = term
+            ax = [operator.index(a) for a in ax]
+        except (TypeError, ValueError):
+            raise ValueError(f"op_apply: term {t} is no (axes, matrix) pair.") from None
+        if not ax:
+            raise ValueError(f"op_apply: term {t} names no axis.")
+        d = 1
+        for q, a in enumerate(ax):
+            if a < 0 or a >= len(ext):
+                raise ValueError(f"op_apply: term {t}: axis {a} is outside the rank {len(ext)}.")
+            if q and a <= ax[q - 1]:
+                raise ValueError(f"op_apply: term {t}: its axes {ax} are not ascending and distinct.")
+            d *= ext[a]
+        if d > OP_MAX_DIM:
+            raise ValueError(f"op_apply: term {t}: the product of its extents is {d}; at most {OP_MAX_DIM} (CTG_OP_MAX_DIM).")
+        raw = np.asarray(mat)
+        if raw.dtype.kind not in "iufbc":
+            raise ValueError(f"op_apply: term {t}: a matrix of dtype {raw.dtype}; numbers are expected.")
+        if raw.shape != (d, d):
+            raise ValueError(f"op_apply: term {t}: a matrix of shape {raw.shape}; ({d}, {d}) is expected.")
+        o = np.ascontiguousarray(raw, dtype=np.complex128)
+        if not np.all(np.isfinite(o.view(np.float64))):
+            raise ValueError(f"op_apply: term {t}: a matrix entry is not finite.")
+        if real and np.any(o.imag != 0.0):
+            raise ValueError(f"op_apply: term {t}: a matrix entry has an imaginary part: O x of a real tensor is not real.")
+        entries += d * d
+        if entries > OP_MAX_ENTRIES:
+            raise ValueError(f"op_apply: more than {OP_MAX_ENTRIES} (CTG_OP_MAX_ENTRIES) matrix entries in all.")
+        naxes.append(len(ax))
+        axes.extend(ax)
+        mats.append(o.view(np.float64).reshape(-1, 2))
+    packed = np.concatenate(mats) if mats else np.zeros((0, 2), dtype=np.float64)
+    return (ext, np.asarray(naxes, dtype=np.int32), np.asarray(axes, dtype=np.int32),
+            np.ascontiguousarray(packed, dtype=np.float64))
+
+
+def op_apply_variant(dtype, extents, terms):
+    """The kernel ``ctg_exec_result_op_apply`` runs for a result of ``dtype`` and shape ``extents`` and the ``terms``
+    (:func:`op_apply_terms`) -- a function of those alone (csrc/ctg_op_apply.hip): ``"op_apply_kernel<T>"`` on the
+    power-of-two route (every extent a power of two, at least 4096 elements), ``"op_apply_general_kernel<T>"``
+    otherwise; ``T`` one of ``float``, ``double``, ``c64``, ``c128``; ``"none"`` for no term (zeros are written
+    without a kernel).  ``ValueError`` for what the call refuses."""
+    t = _DTYPE_TAG[np.dtype(dtype).name]
+    ext, naxes, axes, mats = op_apply_terms(dtype, extents, terms)
+    if naxes.size == 0:
+        return "none"
+    n = 1
+    for v in ext:
+        n *= v
+    return f"op_apply_kernel<{t}>" if _pauli_fast(ext, n) else f"op_apply_general_kernel<{t}>"
 
 
 class DevicePlan:
@@ -784,6 +867,35 @@ class Executor:
         """The name of the kernel ``pauli_apply_result(extents, ops, ...)`` runs on this executor
         (:func:`pauli_apply_variant`)."""
         return pauli_apply_variant(self.plan.dtype, extents, ops)
+
+    # -- dense local operators applied to the result tensor (csrc/ctg_op_apply.hip) -- #
+
+    OP_MAX_DIM = OP_MAX_DIM            # CTG_OP_MAX_DIM
+    OP_MAX_TERMS = OP_MAX_TERMS        # CTG_OP_MAX_TERMS
+    OP_MAX_ENTRIES = OP_MAX_ENTRIES    # CTG_OP_MAX_ENTRIES
+
+    def op_apply_result(self, extents, terms, out_ptr=None):
+        """``y = (sum over t of O_t (x) 1) x`` of the result tensor ``x`` for the dense ``terms``
+        (``ctg_exec_result_op_apply``): ``extents`` is the shape of the result, ``terms`` a sequence of ``(axes,
+        matrix)`` as for :func:`op_apply_terms`, axes of any extent.  Without ``out_ptr``: a numpy array of the
+        result's shape and dtype.  With ``out_ptr``, a device address of ``result_elems`` elements that does not
+        overlap the result tensor: ``y`` is written there and ``None`` returned.  The result tensor is not written.
+        ``ValueError`` for what :func:`op_apply_terms` refuses (nothing is launched), a wrong product of the extents
+        and for a result whose ``sum p`` is not finite."""
+        ext, naxes, axes, mats = op_apply_terms(self.plan.dtype, extents, terms)
+        fn = load().ctg_exec_result_op_apply
+        e = np.ascontiguousarray(ext, dtype=np.int64).reshape(-1)
+        out = None if out_ptr else np.empty(tuple(ext), dtype=np.dtype(self.plan.dtype))
+        i32p = C.POINTER(C.c_int32)
+        _check(fn(self.handle, e.size, _i64p(e), naxes.size, naxes.ctypes.data_as(i32p), axes.ctypes.data_as(i32p),
+                  mats.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(int(out_ptr) if out_ptr else None),
+                  C.c_void_p(None if out is None else out.ctypes.data)))
+        return out
+
+    def op_apply_variant(self, extents, terms):
+        """The name of the kernel ``op_apply_result(extents, terms)`` runs on this executor
+        (:func:`op_apply_variant`)."""
+        return op_apply_variant(self.plan.dtype, extents, terms)
 
     # -- range audit (csrc/ctg_range.hip, cotengra_amd/rangeaudit.py) -- #
 

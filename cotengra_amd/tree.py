@@ -1133,6 +1133,37 @@ class ContractionTree:
             return fn.energy_autograd(*arrays, paulis=paulis, coeffs=coeffs, normalize=normalize)
         return fn.energy(*arrays, paulis=paulis, coeffs=coeffs, wrt=wrt, normalize=normalize)
 
+    def contract_apply_operators(self, arrays, operators, order=None, **kwargs):
+        """:meth:`contract` followed by ``y = (sum over requests of O (x) 1) x`` of the result ``x`` for dense
+        matrices on named output indices of any extent -- ``operators``: a ``(labels, matrix)`` pair or a list of
+        them -- formed on the device next to ``x`` (``HipContractor.apply_operators``, DESIGN.md section 19;
+        ``kwargs``: ``strip_exponent``, ``check_zero``, ``reuse``)."""
+        from .contractor import _tree_contractor
+
+        return _tree_contractor(self, order).apply_operators(*arrays, operators=operators, **kwargs)
+
+    def contract_operator_expectation(self, arrays, operators, order=None, **kwargs):
+        """:meth:`contract` followed by ``<x| O |x>`` of the result for dense matrices on named output indices of
+        any extent (``operators`` as for :meth:`contract_apply_operators`), from reduced density matrices formed on
+        the device (``HipContractor.operator_expectation``; ``kwargs``: ``strip_exponent``, ``check_zero``,
+        ``reuse``).  Not differentiable."""
+        from .contractor import _tree_contractor
+
+        return _tree_contractor(self, order).operator_expectation(*arrays, operators=operators, **kwargs)
+
+    def contract_operator_energy(self, arrays, operators, wrt=None, normalize=False, order=None):
+        """:meth:`contract` followed by the energy ``sum over requests of <x| O |x>`` of the result for Hermitian
+        dense matrices on named output indices of any extent and its gradient by the leaves ``wrt`` (default: all),
+        everything on the device (``HipContractor.operator_energy``).  With ROCm tensors that
+        require grad under grad mode ``energy`` is a 0-d float64 tensor on the device with a ``grad_fn`` (the same
+        bits) and ``grads`` is ``None``, as for :meth:`contract_energy`."""
+        from .contractor import _tree_contractor, _wants_grad
+
+        fn = _tree_contractor(self, order)
+        if _wants_grad(arrays):
+            return fn.operator_energy_autograd(*arrays, operators=operators, normalize=normalize)
+        return fn.operator_energy(*arrays, operators=operators, wrt=wrt, normalize=normalize)
+
     def contract_audit(self, arrays, slices=(0,), order=None):
         """Range audit of the contraction on ``arrays`` (``HipContractor.audit``): the
         slices ``slices`` run step by step, one record per plan step with the exponent statistics of its

@@ -626,6 +626,48 @@ int ctg_exec_result_pauli(ctg_exec* exec, int64_t rank, const int64_t* extents, 
  * entry: after ctg_exec_reduce the root's result tensor holds the total and the call works there (untested). */
 int ctg_exec_result_pauli_apply(ctg_exec* exec, int64_t rank, const int64_t* extents, int64_t m, const uint8_t* ops,
                                 const double* coeffs, void* dev_out, void* host_out);
+/* Added to ABI 10 WITHOUT a bump of CTG_ABI_VERSION likewise (one new symbol; a binding that needs it looks it up):
+ * y = (sum over t of O_t (x) 1) x for small dense matrices O_t on named axes of the result tensor x, of ANY extent,
+ * written on the device (csrc/ctg_op_apply.hip): spin-1 sites, qutrits, boson modes, projectors,
+ * hopping terms, arbitrary few-site observables.  With H = sum O_t Hermitian, conj(2 y) is the cotangent of E = <x| H
+ * |x> for a VJP plan, as for ctg_exec_result_pauli_apply.  Term t acts on naxes[t] >= 1 distinct axes, given in
+ * ascending axis position; axes[] is the concatenation over the terms; D_t is the product of the extents of term t's
+ * axes.  mats holds, term after term, D_t x D_t complex entries as (re, im) pairs of doubles, rows and columns
+ * row-major over the term's axes in that ascending order:
+ *   y[a, r] = sum over t, b of O_t[a, b] x[b, r],     a, b over the term's axes, r over all others,
+ * result_elems elements of the plan's dtype, written to dev_out, to host_out or to both with exactly the staging,
+ * ownership, stream and scratch rules of ctg_exec_result_pauli_apply; the tensor is never written.  CTG_E_NORM when
+ * sum p is not finite; an all-zero tensor gives zeros.  CTG_E_INVALID -- checked on the host before anything is
+ * launched, the tensor and both buffers untouched -- for everything ctg_exec_result_pauli_apply refuses about exec,
+ * rank, extents, the outputs and their overlap with the result tensor; m < 0 or m > CTG_OP_MAX_TERMS; null naxes, axes
+ * or mats with m > 0; a term with no axis, an axis out of range, repeated or not ascending within a term; D_t >
+ * CTG_OP_MAX_DIM (= CTG_RDM_MAX_DIM: every term's expectation value can come from one reduced density matrix); more
+ * than CTG_OP_MAX_ENTRIES matrix entries (sum of D_t^2) in all; a matrix entry that is not finite and, on real plans, a
+ * non-zero imaginary part.  m = 0 writes zeros.
+ *   - Arithmetic: per element j a complex fp64 accumulator starts at +0; terms in the caller's order; inside a term b
+ *     = 0 .. D_t - 1 ascending (ascending partner flat index, because the axes ascend).  With p = x[partner(j, b)] in
+ *     fp64 and W = O_t[a(j), b]: acc_re += (W_re p_re - W_im p_im), acc_im += (W_re p_im + W_im p_re) -- four products,
+ *     the difference / sum and the addition each rounded once, nothing fused; real plans: acc += W_re p.  After the last
+ *     term acc is rounded once to the plan's dtype.  An entry that is zero in both parts may be skipped: it would add
+ *     +-0 to an accumulator that is never -0, so for a finite tensor no bit changes.
+ *   - No atomics and no sum across threads: the bits of y are a function of (dtype, extents, the terms in order, the
+ *     tensor's bytes) alone -- not of the executor, the grid, earlier calls in the scratch, or which output was asked.
+ *   - Per real component |y[j] - exact| <= (N + 2) 2^-53 sum over t, b of (|Re W| + |Im W|)(|Re p| + |Im p|) + u |y[j]|,
+ *     N = sum of D_t, u = 2^-24 for float / complex64 plans and 2^-53 for double / complex128 (first order).
+ * Every extent a power of two and at least 4096 elements: "op_apply_kernel<T>", T in float | double | c64 | c128, one
+ * launch with the geometry of pauli_apply_kernel (256 threads, two workgroups per CU, chunks of 4096 elements, grid =
+ * min(512, ceil(chunks / 3)), 16 elements' accumulators per thread).  A term's flat-index bits below 12 lie inside a
+ * chunk, those above are uniform over it: per term the workgroup walks the partner chunks in ascending order, stages
+ * each in LDS and reads its partners and the block of O_t (LDS when at most 8 KiB, else the scratch) from there; a
+ * partner chunk whose whole block of O_t is zero is not read (a diagonal term reads the tensor once).  Any other shape:
+ * "op_apply_general_kernel<T>", a thread per output element, same order; not tuned.  Scratch: 456 bytes per term
+ * (general route: 88), 16 bytes per matrix entry (16 MiB at most), 8 bytes per block, plus the staged y.  No multi-rank
+ * entry, as above. */
+#define CTG_OP_MAX_DIM 64
+#define CTG_OP_MAX_TERMS 4096
+#define CTG_OP_MAX_ENTRIES (1 << 20)
+int ctg_exec_result_op_apply(ctg_exec* exec, int64_t rank, const int64_t* extents, int64_t m, const int32_t* naxes,
+                             const int32_t* axes, const double* mats, void* dev_out, void* host_out);
 /* debugging aid: copy `n` elements of the arena starting at element `offset`
  * to the host (synchronous) */
 int ctg_exec_download_arena(ctg_exec* exec, int64_t offset, int64_t n, void* host_out);
