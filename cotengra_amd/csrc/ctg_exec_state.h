@@ -1,6 +1,9 @@
 // ctg_exec_state.h -- the opaque handles of include/ctg_hip.h as seen by the
-// host-side translation units of the library (ctg_runtime.hip,
-// ctg_collective.hip).  Not installed; not part of the ABI.
+// host-side translation units of the library: ctg_runtime.hip, ctg_collective.hip,
+// ctg_lds_host.hip, ctg_range.hip and, through
+// ctg_result_host.h, the sources that read the result tensor (ctg_sample.hip,
+// ctg_reduce.hip, ctg_rdm.hip, ctg_pauli.hip, ctg_pauli_apply.hip, ctg_op_apply.hip).
+// Not installed; not part of the ABI.
 #pragma once
 
 #include <string>
@@ -219,7 +222,8 @@ struct MarginalPlan {
 // CTG_OK, or CTG_E_INVALID with *why set
 __attribute__((visibility("hidden"))) int marginal_plan(int64_t rank, const int64_t* extents, const int32_t* keep,
                                                         int64_t result_elems, MarginalPlan* out, const char** why);
-// the executor's scratch of ctg_reduce.hip / ctg_rdm.hip / ctg_pauli.hip (d_reduce), at least `want` bytes; the stream must be idle
+// the executor's scratch of ctg_reduce.hip / ctg_rdm.hip / ctg_pauli.hip / ctg_pauli_apply.hip / ctg_op_apply.hip (d_reduce, laid
+// out by Carve of ctg_result_host.h), at least `want` bytes; the stream must be idle
 // (the statistics call synchronised it).  CTG_OK, CTG_E_NOMEM or CTG_E_HIP with the error set.
 __attribute__((visibility("hidden"))) int reduce_reserve(ctg_exec* e, int64_t want);
 }

@@ -12,7 +12,7 @@
 //     D_t - 1 ascending (ascending partner flat index, because the axes ascend);
 //   - with p = x[partner(j, b)] widened to fp64 and W = O_t[a(j), b]:  acc_re <- acc_re + (W_re p_re - W_im p_im),
 //     acc_im <- acc_im + (W_re p_im + W_im p_re); the four products, the difference / sum and the addition to acc each
-//     rounded once, nothing fused (fp contract(off)) -- ApplyElem<T>::mac of ctg_pauli_apply.hip;  real plans: acc <- acc
+//     rounded once, nothing fused (fp contract(off)) -- ApplyElem<T>::mac of ctg_result_elem.h;  real plans: acc <- acc
 //     + W_re p;
 //   - after the last term acc is rounded once to the plan's dtype.
 // No atomics; no sum crosses a thread: the bits of y are a function of (dtype, extents, terms in order, the tensor's
@@ -20,7 +20,7 @@
 // is never -0 (it starts at +0, and x + (-x) rounds to +0), so for a finite tensor -- the call refuses any other --
 // no bit changes.  Both kernels skip; where, is said at the place.
 //
-//   power of two (every extent a power of two, at least kOpChunk = 4096 elements):
+//   power of two (every extent a power of two, at least kResultChunk = 4096 elements):
 //
 //     op_apply_kernel<T>   the geometry of pauli_apply_kernel: 256 threads, two workgroups per CU, one launch; a
 //                          workgroup owns the output chunks wg, wg + grid, ... of 4096 elements, grid = min(512,
@@ -45,37 +45,27 @@
 //   general (any other shape): op_apply_general_kernel<T>, a thread per output element (grid-stride); a(j) and the
 //   partners from the digits (j / stride) % extent; same order; an entry that is zero is skipped; not tuned.
 //
-// Scratch (the buffer of ctg_reduce.hip / ctg_rdm.hip / ctg_pauli.hip, reduce_reserve): 456 bytes per term (general
+// Scratch (the executor's d_reduce, reduce_reserve): 456 bytes per term (general
 // route: 88), the matrices (16 bytes per entry, 8 on real plans of the power-of-two route: at most 16 MiB), 8 bytes per
 // block and, when only host_out is given, result_elems elements of y.
 #include <algorithm>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <vector>
 
-#include "ctg_exec_state.h"
-#include "ctg_sample_elem.h"
+#include "ctg_result_elem.h"
+#include "ctg_result_host.h"
 
 namespace ctg {
 
-constexpr int kOpChunk = kSampleBlock;   // elements of a chunk
-constexpr int kOpBits = 12;              // log2(kOpChunk)
-constexpr int kOpMaxGrid = 512;          // workgroups of op_apply_kernel
-constexpr int kOpMinChunks = 3;          // chunks per workgroup before the grid grows
 constexpr int kOpMatLds = 1024;          // doubles of a block kept in LDS (8 KiB)
 constexpr int kOpMaxAxes = 6;            // axes of extent >= 2 of a term (D <= 64)
 constexpr int64_t kOpGeneralMaxBlocks = 1 << 20;
-static_assert(kOpChunk == 1 << kOpBits, "a chunk is addressed by kOpBits bits");
 static_assert(CTG_OP_MAX_DIM == 1 << kOpMaxAxes, "a column mask has one bit per b_lo");
 
 // What a term of the power-of-two route needs on the device
 struct OpTermMeta {
-    int64_t hi;              // its flat-index bits at and above kOpBits, shifted down: bits of the chunk index
+    int64_t hi;              // its flat-index bits at and above kResultChunkBits, shifted down: bits of the chunk index
     int64_t blocks;          // where its blocks start in the matrices (in doubles)
     int64_t cmask;           // where its 2^nhi x 2^nhi column masks start
-    int32_t lo;              // its flat-index bits below kOpBits
+    int32_t lo;              // its flat-index bits below kResultChunkBits
     int32_t nlo, nhi;
     int32_t in_lds;          // 1: a block is at most kOpMatLds doubles
     uint8_t hipos[8];        // the positions of the bits of hi, ascending
@@ -93,73 +83,22 @@ struct OpGenTerm {
     int32_t nax, dim;
 };
 
-// acc += W p as the header defines it (the arithmetic of ApplyElem<T>::mac, ctg_pauli_apply.hip); the rounding to T
-template <typename T> struct OpElem;
-template <> struct OpElem<float> {
-    static constexpr int P = 1;
-    typedef double W;
-    static __device__ __forceinline__ void mac(float p, W w, double& are, double&) {
-#pragma clang fp contract(off)
-        const double a = w * (double)p;
-        are = are + a;
-    }
-    static __device__ __forceinline__ float round(double are, double) { return (float)are; }
-};
-template <> struct OpElem<double> {
-    static constexpr int P = 1;
-    typedef double W;
-    static __device__ __forceinline__ void mac(double p, W w, double& are, double&) {
-#pragma clang fp contract(off)
-        const double a = w * p;
-        are = are + a;
-    }
-    static __device__ __forceinline__ double round(double are, double) { return are; }
-};
-template <> struct OpElem<float2> {
-    static constexpr int P = 2;
-    typedef double2 W;
-    static __device__ __forceinline__ void mac(float2 p, W w, double& are, double& aim) {
-#pragma clang fp contract(off)
-        const double pr = (double)p.x, pi = (double)p.y;
-        const double a = w.x * pr, b = w.y * pi, c = w.x * pi, d = w.y * pr;
-        const double tr = a - b, ti = c + d;
-        are = are + tr;
-        aim = aim + ti;
-    }
-    static __device__ __forceinline__ float2 round(double are, double aim) { return make_float2((float)are, (float)aim); }
-};
-template <> struct OpElem<double2> {
-    static constexpr int P = 2;
-    typedef double2 W;
-    static __device__ __forceinline__ void mac(double2 p, W w, double& are, double& aim) {
-#pragma clang fp contract(off)
-        const double a = w.x * p.x, b = w.y * p.y, c = w.x * p.y, d = w.y * p.x;
-        const double tr = a - b, ti = c + d;
-        are = are + tr;
-        aim = aim + ti;
-    }
-    static __device__ __forceinline__ double2 round(double are, double aim) { return make_double2(are, aim); }
-};
-
+// (acc += W p, the type W of a stored weight and the rounding of acc to T: ApplyElem<T> of ctg_result_elem.h)
 template <typename T>
 __global__ __launch_bounds__(kSampleThreads, 2) void op_apply_kernel(const T* __restrict__ x, int64_t n, int vec, int vec_out,
                                                                      int64_t nchunks, const OpTermMeta* __restrict__ terms, int nterms,
                                                                      const double* __restrict__ mats,
                                                                      const unsigned long long* __restrict__ cmasks, T* __restrict__ y) {
 #pragma clang fp contract(off)
-    typedef typename OpElem<T>::W W;
-    constexpr int P = OpElem<T>::P;
+    typedef typename ApplyElem<T>::W W;
+    constexpr int P = ApplyElem<T>::P;
     constexpr int V = 16 / sizeof(T);
     constexpr int LV = V == 4 ? 2 : V == 2 ? 1 : 0;
-    constexpr int G = kOpChunk / V / kSampleThreads;
+    constexpr int G = kResultChunk / V / kSampleThreads;
     constexpr int E = G * V;   // elements of a thread: 16
     static_assert(G <= 16 && V <= 4, "ag and ak of OpTermMeta");
-    __shared__ __attribute__((aligned(16))) unsigned char raw[kOpChunk * (int)sizeof(T)];
+    __shared__ __attribute__((aligned(16))) unsigned char raw[kResultChunk * (int)sizeof(T)];
     __shared__ __attribute__((aligned(16))) double lmat[kOpMatLds];
-    union Group {
-        uint4 raw;
-        T v[V];
-    };
     uint4* l4 = reinterpret_cast<uint4*>(raw);
     const T* lx = reinterpret_cast<const T*>(raw);
     const int tid = threadIdx.x;
@@ -198,24 +137,24 @@ __global__ __launch_bounds__(kSampleThreads, 2) void op_apply_kernel(const T* __
                 if (!cm) continue;
                 int64_t c2 = c0;
                 for (int q = 0; q < nhi; ++q) c2 |= (int64_t)((b_hi >> q) & 1) << tm->hipos[q];
-                const int64_t base2 = c2 << kOpBits;
+                const int64_t base2 = c2 << kResultChunkBits;
                 const W* blk = reinterpret_cast<const W*>(mats + tm->blocks + ((int64_t)a_hi * NH + b_hi) * NL * NL * P);
                 if (!lo) {
                     // the partner is the thread's own position in chunk c2: no LDS, no barrier; one entry
                     const W w = blk[0];
 #pragma unroll
                     for (int g = 0; g < G; ++g) {
-                        Group pg;
+                        Group<T> pg;
                         load_group<T>(x, base2 + (int64_t)(g * kSampleThreads + tid) * V, n, vec != 0, pg.v);
 #pragma unroll
-                        for (int k = 0; k < V; ++k) OpElem<T>::mac(pg.v[k], w, acc_re[g * V + k], acc_im[P == 2 ? g * V + k : 0]);
+                        for (int k = 0; k < V; ++k) ApplyElem<T>::mac(pg.v[k], w, acc_re[g * V + k], acc_im[P == 2 ? g * V + k : 0]);
                     }
                     continue;
                 }
                 __syncthreads();   // (the block before has read the copies)
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
-                    Group s;
+                    Group<T> s;
                     load_group<T>(x, base2 + (int64_t)(g * kSampleThreads + tid) * V, n, vec != 0, s.v);
                     l4[g * kSampleThreads + tid] = s.raw;
                 }
@@ -232,7 +171,7 @@ __global__ __launch_bounds__(kSampleThreads, 2) void op_apply_kernel(const T* __
                         const uint32_t d = tm->dep[b_lo];
                         const W* col = lw + b_lo * NL;
 #pragma unroll
-                        for (int i = 0; i < E; ++i) OpElem<T>::mac(lx[pos0[i] | d], col[alo[i]], acc_re[i], acc_im[P == 2 ? i : 0]);
+                        for (int i = 0; i < E; ++i) ApplyElem<T>::mac(lx[pos0[i] | d], col[alo[i]], acc_re[i], acc_im[P == 2 ? i : 0]);
                     }
                 } else {
                     for (int b_lo = 0; b_lo < NL; ++b_lo) {
@@ -240,17 +179,17 @@ __global__ __launch_bounds__(kSampleThreads, 2) void op_apply_kernel(const T* __
                         const uint32_t d = tm->dep[b_lo];
                         const W* col = blk + b_lo * NL;
 #pragma unroll
-                        for (int i = 0; i < E; ++i) OpElem<T>::mac(lx[pos0[i] | d], col[alo[i]], acc_re[i], acc_im[P == 2 ? i : 0]);
+                        for (int i = 0; i < E; ++i) ApplyElem<T>::mac(lx[pos0[i] | d], col[alo[i]], acc_re[i], acc_im[P == 2 ? i : 0]);
                     }
                 }
             }
         }
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-            Group o;
+            Group<T> o;
 #pragma unroll
-            for (int k = 0; k < V; ++k) o.v[k] = OpElem<T>::round(acc_re[g * V + k], acc_im[P == 2 ? g * V + k : 0]);
-            const int64_t e = (c << kOpBits) + (int64_t)(g * kSampleThreads + tid) * V;   // (e + V <= n: n is a multiple of 4096)
+            for (int k = 0; k < V; ++k) o.v[k] = ApplyElem<T>::round(acc_re[g * V + k], acc_im[P == 2 ? g * V + k : 0]);
+            const int64_t e = (c << kResultChunkBits) + (int64_t)(g * kSampleThreads + tid) * V;   // (e + V <= n: n is a multiple of 4096)
             if (vec_out) {
                 *reinterpret_cast<uint4*>(y + e) = o.raw;
             } else {
@@ -266,8 +205,6 @@ __global__ __launch_bounds__(kSampleThreads) void op_apply_general_kernel(const 
                                                                           const OpGenTerm* __restrict__ terms, int nterms,
                                                                           const double* __restrict__ mats, T* __restrict__ y) {
 #pragma clang fp contract(off)
-    typedef typename OpElem<T>::W W;
-    constexpr int P = OpElem<T>::P;
     for (int64_t j = (int64_t)blockIdx.x * kSampleThreads + threadIdx.x; j < n; j += (int64_t)gridDim.x * kSampleThreads) {
         double are = 0.0, aim = 0.0;
         for (int t = 0; t < nterms; ++t) {
@@ -290,15 +227,10 @@ __global__ __launch_bounds__(kSampleThreads) void op_apply_general_kernel(const 
                     off += (rem % tm->ext[q]) * tm->stride[q];
                     rem /= tm->ext[q];
                 }
-                W w;
-                if constexpr (P == 2)
-                    w = make_double2(wre, wim);
-                else
-                    w = wre;
-                OpElem<T>::mac(x[j0 + off], w, are, aim);
+                ApplyElem<T>::mac(x[j0 + off], wre, wim, are, aim);
             }
         }
-        y[j] = OpElem<T>::round(are, aim);
+        y[j] = ApplyElem<T>::round(are, aim);
     }
 }
 
@@ -308,70 +240,15 @@ using namespace ctg;
 
 namespace {
 
-int ofail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    ctg_set_error_(buf);
-    return code;
-}
-
-#define HIP_TRY_O(expr)                                                                                    \
-    do {                                                                                                   \
-        hipError_t _e = (expr);                                                                            \
-        if (_e != hipSuccess)                                                                              \
-            return ofail(_e == hipErrorOutOfMemory ? CTG_E_NOMEM : CTG_E_HIP, "%s failed: %s", #expr,      \
-                         hipGetErrorString(_e));                                                           \
-    } while (0)
-
-#define LAUNCH_CHECK_O(name)                                                                               \
-    do {                                                                                                   \
-        hipError_t _e = hipGetLastError();                                                                 \
-        if (_e != hipSuccess) return ofail(CTG_E_HIP, name " launch failed: %s", hipGetErrorString(_e));   \
-    } while (0)
-
-int64_t up256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
-// host -> device from a vector of the caller's frame, complete on return: no copy outlives the frame, on any path
-hipError_t upload(void* dst, const void* src, int64_t bytes, hipStream_t st) {
-    const hipError_t e = hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, st);
-    return e != hipSuccess ? e : hipStreamSynchronize(st);
-}
-
-// the bits of v at the set bits of mask, packed (pext); v's low bits spread over the set bits of mask (pdep)
-uint32_t extract_bits(uint32_t v, uint32_t mask) {
-    uint32_t out = 0;
-    int q = 0;
-    for (int bit = 0; bit < 32; ++bit)
-        if ((mask >> bit) & 1u) {
-            out |= ((v >> bit) & 1u) << q;
-            ++q;
-        }
-    return out;
-}
-uint32_t deposit_bits(uint32_t v, uint32_t mask) {
-    uint32_t out = 0;
-    int q = 0;
-    for (int bit = 0; bit < 32; ++bit)
-        if ((mask >> bit) & 1u) {
-            out |= ((v >> q) & 1u) << bit;
-            ++q;
-        }
-    return out;
-}
-
 template <typename T>
 int op_fast_launch(ctg_exec* e, int64_t n, const OpTermMeta* d_terms, int nterms, const double* d_mats,
                    const unsigned long long* d_cmasks, void* y) {
     const int vec = ((uintptr_t)e->d_result & 15) == 0 ? 1 : 0;
     const int vec_out = ((uintptr_t)y & 15) == 0 ? 1 : 0;
-    const int64_t nchunks = n / kOpChunk;
-    const int grid = (int)std::min<int64_t>(kOpMaxGrid, (nchunks + kOpMinChunks - 1) / kOpMinChunks);
-    op_apply_kernel<T><<<dim3((unsigned)grid), dim3(kSampleThreads), 0, e->stream>>>((const T*)e->d_result, n, vec, vec_out, nchunks,
+    const int64_t nchunks = n / kResultChunk;
+    op_apply_kernel<T><<<dim3((unsigned)result_chunk_grid(nchunks)), dim3(kSampleThreads), 0, e->stream>>>((const T*)e->d_result, n, vec, vec_out, nchunks,
                                                                                       d_terms, nterms, d_mats, d_cmasks, (T*)y);
-    LAUNCH_CHECK_O("op_apply_kernel");
+    LAUNCH_CHECK("op_apply_kernel");
     return CTG_OK;
 }
 
@@ -380,7 +257,7 @@ int op_general_launch(ctg_exec* e, int64_t n, const OpGenTerm* d_terms, int nter
     const int64_t blocks = std::min<int64_t>(kOpGeneralMaxBlocks, (n + kSampleThreads - 1) / kSampleThreads);
     op_apply_general_kernel<T><<<dim3((unsigned)blocks), dim3(kSampleThreads), 0, e->stream>>>((const T*)e->d_result, n, d_terms, nterms,
                                                                                                 d_mats, (T*)y);
-    LAUNCH_CHECK_O("op_apply_general_kernel");
+    LAUNCH_CHECK("op_apply_general_kernel");
     return CTG_OK;
 }
 
@@ -388,89 +265,59 @@ int op_general_launch(ctg_exec* e, int64_t n, const OpGenTerm* d_terms, int nter
 
 extern "C" int ctg_exec_result_op_apply(ctg_exec* e, int64_t rank, const int64_t* extents, int64_t m, const int32_t* naxes,
                                         const int32_t* axes, const double* mats, void* dev_out, void* host_out) {
-    if (!e || !extents) return ofail(CTG_E_INVALID, "op_apply: null argument");
-    if (!dev_out && !host_out) return ofail(CTG_E_INVALID, "op_apply: neither dev_out nor host_out is given");
-    if (rank < 0) return ofail(CTG_E_INVALID, "op_apply: negative rank");
-    int64_t n = 1;
-    bool pow2 = true;
-    for (int64_t a = 0; a < rank; ++a) {
-        if (extents[a] < 1) return ofail(CTG_E_INVALID, "op_apply: an extent is not positive");
-        if (extents[a] > kReduceMaxElems / n) return ofail(CTG_E_INVALID, "op_apply: the extents' product does not equal result_elems");
-        n *= extents[a];
-        pow2 = pow2 && (extents[a] & (extents[a] - 1)) == 0;
-    }
-    if (n != e->plan->result_elems) return ofail(CTG_E_INVALID, "op_apply: the extents' product does not equal result_elems");
+    if (!e || !extents) return result_fail(CTG_E_INVALID, "op_apply: null argument");
+    ApplyOut out{"op_apply", dev_out, host_out};
+    if (out.given() != CTG_OK) return CTG_E_INVALID;
+    ResultShape shape;
+    const char* why = "";
+    if (result_shape(rank, extents, e->plan->result_elems, &shape, &why) != CTG_OK)
+        return result_fail(CTG_E_INVALID, "op_apply: %s", why);
+    const int64_t n = shape.n;
+    const std::vector<int64_t>& stride = shape.strides;
     if (m < 0 || m > CTG_OP_MAX_TERMS)
-        return ofail(CTG_E_INVALID, "op_apply: %lld terms; between 0 and CTG_OP_MAX_TERMS = %d", (long long)m, CTG_OP_MAX_TERMS);
-    if (m > 0 && (!naxes || !axes || !mats)) return ofail(CTG_E_INVALID, "op_apply: null naxes, axes or mats");
+        return result_fail(CTG_E_INVALID, "op_apply: %lld terms; between 0 and CTG_OP_MAX_TERMS = %d", (long long)m, CTG_OP_MAX_TERMS);
+    if (m > 0 && (!naxes || !axes || !mats)) return result_fail(CTG_E_INVALID, "op_apply: null naxes, axes or mats");
     const int dtype = e->plan->dtype;
     const bool real = dtype == CTG_F32 || dtype == CTG_F64;
-    const int64_t item = ctg_item_size(dtype), bytes = n * item;
-    if (dev_out) {
-        const uintptr_t d0 = (uintptr_t)dev_out, r0 = (uintptr_t)e->d_result;
-        if (d0 < r0 + (uintptr_t)bytes && r0 < d0 + (uintptr_t)bytes)
-            return ofail(CTG_E_INVALID, "op_apply: dev_out overlaps the result tensor");
-    }
+    const int64_t item = ctg_item_size(dtype);
+    if (out.overlap(e, n * item) != CTG_OK) return CTG_E_INVALID;
     // per term: where its axes and its matrix start, and D
     std::vector<int64_t> ax0((size_t)m), mat0((size_t)m);
     std::vector<int> dim((size_t)m);
     int64_t nax_total = 0, entries = 0;
     for (int64_t t = 0; t < m; ++t) {
-        if (naxes[t] < 1) return ofail(CTG_E_INVALID, "op_apply: term %lld names %d axes; at least one is expected", (long long)t, (int)naxes[t]);
-        if (naxes[t] > rank) return ofail(CTG_E_INVALID, "op_apply: term %lld names %d axes of a tensor of rank %lld", (long long)t, (int)naxes[t], (long long)rank);
+        if (naxes[t] < 1) return result_fail(CTG_E_INVALID, "op_apply: term %lld names %d axes; at least one is expected", (long long)t, (int)naxes[t]);
+        if (naxes[t] > rank) return result_fail(CTG_E_INVALID, "op_apply: term %lld names %d axes of a tensor of rank %lld", (long long)t, (int)naxes[t], (long long)rank);
         ax0[t] = nax_total;
         int64_t d = 1;
         for (int32_t q = 0; q < naxes[t]; ++q) {
             const int32_t a = axes[nax_total + q];
-            if (a < 0 || a >= rank) return ofail(CTG_E_INVALID, "op_apply: term %lld: axis %d is outside the rank %lld", (long long)t, (int)a, (long long)rank);
+            if (a < 0 || a >= rank) return result_fail(CTG_E_INVALID, "op_apply: term %lld: axis %d is outside the rank %lld", (long long)t, (int)a, (long long)rank);
             if (q > 0 && a <= axes[nax_total + q - 1])
-                return ofail(CTG_E_INVALID, "op_apply: term %lld: its axes are not ascending and distinct", (long long)t);
+                return result_fail(CTG_E_INVALID, "op_apply: term %lld: its axes are not ascending and distinct", (long long)t);
             d *= extents[a];
             if (d > CTG_OP_MAX_DIM)
-                return ofail(CTG_E_INVALID, "op_apply: term %lld: the product of its extents exceeds CTG_OP_MAX_DIM = %d", (long long)t, CTG_OP_MAX_DIM);
+                return result_fail(CTG_E_INVALID, "op_apply: term %lld: the product of its extents exceeds CTG_OP_MAX_DIM = %d", (long long)t, CTG_OP_MAX_DIM);
         }
         nax_total += naxes[t];
         dim[t] = (int)d;
         mat0[t] = 2 * entries;
         entries += d * d;
         if (entries > CTG_OP_MAX_ENTRIES)
-            return ofail(CTG_E_INVALID, "op_apply: more than CTG_OP_MAX_ENTRIES = %d matrix entries", CTG_OP_MAX_ENTRIES);
+            return result_fail(CTG_E_INVALID, "op_apply: more than CTG_OP_MAX_ENTRIES = %d matrix entries", CTG_OP_MAX_ENTRIES);
     }
     for (int64_t i = 0; i < entries; ++i) {
-        if (!std::isfinite(mats[2 * i]) || !std::isfinite(mats[2 * i + 1])) return ofail(CTG_E_INVALID, "op_apply: matrix entry %lld is not finite", (long long)i);
+        if (!std::isfinite(mats[2 * i]) || !std::isfinite(mats[2 * i + 1])) return result_fail(CTG_E_INVALID, "op_apply: matrix entry %lld is not finite", (long long)i);
         if (real && mats[2 * i + 1] != 0.0)
-            return ofail(CTG_E_INVALID, "op_apply: matrix entry %lld has an imaginary part: O x of a real tensor is not real", (long long)i);
+            return result_fail(CTG_E_INVALID, "op_apply: matrix entry %lld has an imaginary part: O x of a real tensor is not real", (long long)i);
     }
     hipStream_t st = e->stream;
-    if (m == 0) {
-        if (dev_out) {
-            HIP_TRY_O(hipMemsetAsync(dev_out, 0, (size_t)bytes, st));
-            HIP_TRY_O(hipStreamSynchronize(st));
-        }
-        if (host_out) memset(host_out, 0, (size_t)bytes);
-        return CTG_OK;
-    }
-    {
-        // sum p of the result by the statistics passes of ctg_sample.hip (synchronises)
-        double sum_p = 0.0;
-        const int rc = ctg_exec_result_stats(e, &sum_p, nullptr, nullptr, nullptr);
-        if (rc != CTG_OK) return rc;
-        if (!std::isfinite(sum_p)) return ofail(CTG_E_NORM, "the result tensor's sum of |x|^2 is %g: no operator is applied to it", sum_p);
-    }
-    std::vector<int64_t> stride((size_t)rank);
-    {
-        int64_t s = 1;
-        for (int64_t a = rank - 1; a >= 0; --a) {
-            stride[a] = s;
-            s *= extents[a];
-        }
-    }
-    const int64_t stage_bytes = dev_out ? 0 : up256(bytes);
-    const bool fast = pow2 && n >= kOpChunk;
-    void* y = dev_out;
-    int rc;
-    if (fast) {
-        const int LV = item == 4 ? 2 : item == 8 ? 1 : 0, V = 1 << LV, G = kOpChunk / V / kSampleThreads, P = real ? 1 : 2;
+    if (m == 0) return out.zero(st);
+    int rc = result_norm_finite(e, "no operator is applied to it");
+    if (rc != CTG_OK) return rc;
+    void* y = nullptr;
+    if (shape.pow2 && n >= kResultChunk) {
+        const int LV = item == 4 ? 2 : item == 8 ? 1 : 0, V = 1 << LV, G = kResultChunk / V / kSampleThreads, P = real ? 1 : 2;
         std::vector<OpTermMeta> metas((size_t)m);
         std::vector<double> blocks;
         std::vector<unsigned long long> cmasks;
@@ -483,8 +330,8 @@ extern "C" int ctg_exec_result_op_apply(ctg_exec* e, int64_t rank, const int64_t
             }
             OpTermMeta& tm = metas[t];
             memset(&tm, 0, sizeof(tm));
-            tm.lo = (int32_t)(mask & (kOpChunk - 1));
-            tm.hi = mask >> kOpBits;
+            tm.lo = (int32_t)(mask & (kResultChunk - 1));
+            tm.hi = mask >> kResultChunkBits;
             tm.nlo = __builtin_popcount((unsigned)tm.lo);
             tm.nhi = __builtin_popcountll((unsigned long long)tm.hi);
             const int NL = 1 << tm.nlo, NH = 1 << tm.nhi, D = dim[t];   // (NL NH = D: the axes ascend, so a = (a_hi, a_lo))
@@ -517,21 +364,24 @@ extern "C" int ctg_exec_result_op_apply(ctg_exec* e, int64_t rank, const int64_t
         }
         // [the terms | their blocks | the column masks | y, when it is staged for host_out]
         const int64_t t_bytes = m * (int64_t)sizeof(OpTermMeta), b_bytes = (int64_t)blocks.size() * 8, c_bytes = (int64_t)cmasks.size() * 8;
-        rc = reduce_reserve(e, up256(t_bytes) + up256(b_bytes) + up256(c_bytes) + stage_bytes);
+        OpTermMeta* d_terms = nullptr;
+        double* d_blocks = nullptr;
+        unsigned long long* d_cmasks = nullptr;
+        auto lay = [&](void* base) {
+            Carve c(base);
+            d_terms = c.take<OpTermMeta>(t_bytes);
+            d_blocks = c.take<double>(b_bytes);
+            d_cmasks = c.take<unsigned long long>(c_bytes);
+            y = out.y(c.take<char>(out.stage_bytes()));
+            return c.bytes();
+        };
+        rc = reduce_reserve(e, lay(nullptr));
         if (rc != CTG_OK) return rc;
-        OpTermMeta* d_terms = (OpTermMeta*)e->d_reduce;
-        double* d_blocks = (double*)((char*)d_terms + up256(t_bytes));
-        unsigned long long* d_cmasks = (unsigned long long*)((char*)d_blocks + up256(b_bytes));
-        if (!y) y = (char*)d_cmasks + up256(c_bytes);
-        HIP_TRY_O(upload(d_terms, metas.data(), t_bytes, st));
-        HIP_TRY_O(upload(d_blocks, blocks.data(), b_bytes, st));
-        HIP_TRY_O(upload(d_cmasks, cmasks.data(), c_bytes, st));
-        switch (dtype) {
-            case CTG_F32: rc = op_fast_launch<float>(e, n, d_terms, (int)m, d_blocks, d_cmasks, y); break;
-            case CTG_F64: rc = op_fast_launch<double>(e, n, d_terms, (int)m, d_blocks, d_cmasks, y); break;
-            case CTG_C64: rc = op_fast_launch<float2>(e, n, d_terms, (int)m, d_blocks, d_cmasks, y); break;
-            default: rc = op_fast_launch<double2>(e, n, d_terms, (int)m, d_blocks, d_cmasks, y); break;
-        }
+        lay(e->d_reduce);
+        HIP_TRY(upload(d_terms, metas.data(), t_bytes, st));
+        HIP_TRY(upload(d_blocks, blocks.data(), b_bytes, st));
+        HIP_TRY(upload(d_cmasks, cmasks.data(), c_bytes, st));
+        rc = dispatch_elem(dtype, [&](auto t) { return op_fast_launch<decltype(t)>(e, n, d_terms, (int)m, d_blocks, d_cmasks, y); });
     } else {
         std::vector<OpGenTerm> terms((size_t)m);
         for (int64_t t = 0; t < m; ++t) {
@@ -549,22 +399,21 @@ extern "C" int ctg_exec_result_op_apply(ctg_exec* e, int64_t rank, const int64_t
         }
         // [the terms | the matrices as given | y, when it is staged for host_out]
         const int64_t t_bytes = m * (int64_t)sizeof(OpGenTerm), b_bytes = entries * 16;
-        rc = reduce_reserve(e, up256(t_bytes) + up256(b_bytes) + stage_bytes);
+        OpGenTerm* d_terms = nullptr;
+        double* d_mats = nullptr;
+        auto lay = [&](void* base) {
+            Carve c(base);
+            d_terms = c.take<OpGenTerm>(t_bytes);
+            d_mats = c.take<double>(b_bytes);
+            y = out.y(c.take<char>(out.stage_bytes()));
+            return c.bytes();
+        };
+        rc = reduce_reserve(e, lay(nullptr));
         if (rc != CTG_OK) return rc;
-        OpGenTerm* d_terms = (OpGenTerm*)e->d_reduce;
-        double* d_mats = (double*)((char*)d_terms + up256(t_bytes));
-        if (!y) y = (char*)d_mats + up256(b_bytes);
-        HIP_TRY_O(upload(d_terms, terms.data(), t_bytes, st));
-        HIP_TRY_O(upload(d_mats, mats, b_bytes, st));
-        switch (dtype) {
-            case CTG_F32: rc = op_general_launch<float>(e, n, d_terms, (int)m, d_mats, y); break;
-            case CTG_F64: rc = op_general_launch<double>(e, n, d_terms, (int)m, d_mats, y); break;
-            case CTG_C64: rc = op_general_launch<float2>(e, n, d_terms, (int)m, d_mats, y); break;
-            default: rc = op_general_launch<double2>(e, n, d_terms, (int)m, d_mats, y); break;
-        }
+        lay(e->d_reduce);
+        HIP_TRY(upload(d_terms, terms.data(), t_bytes, st));
+        HIP_TRY(upload(d_mats, mats, b_bytes, st));
+        rc = dispatch_elem(dtype, [&](auto t) { return op_general_launch<decltype(t)>(e, n, d_terms, (int)m, d_mats, y); });
     }
-    if (rc != CTG_OK) return rc;
-    if (host_out) HIP_TRY_O(hipMemcpyAsync(host_out, y, (size_t)bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY_O(hipStreamSynchronize(st));
-    return CTG_OK;
+    return out.finish(rc, y, st);
 }

@@ -16,7 +16,7 @@
 // The host groups the strings of a call by xm (groups in order of first appearance, the caller's order inside a group)
 // and runs every group in passes of at most kPauliPass = 32 strings; a pass reads the tensor once.  Two routes:
 //
-//   power of two (every extent a power of two, at least kPauliChunk = 4096 elements):
+//   power of two (every extent a power of two, at least kResultChunk = 4096 elements):
 //
 //     pauli_chunk_kernel<T>   256 threads, two workgroups per CU.  A chunk is 4096 consecutive elements, thread t holds
 //                             the 16-byte groups g 256 + t (load_group).  xm = xm_hi 4096 + xm_lo:
@@ -40,7 +40,7 @@
 //     pauli_finish_kernel     adds those in ascending order, multiplies by (-1)^ceil(ny / 2) (x 2 for xm != 0) and
 //                             writes the value to the string's place in the caller's order.
 //
-//     grid = min(kPauliMaxGrid, ceil(units / kPauliMinUnits)), units = chunks (xm_hi = 0) or chunk pairs: a function
+//     grid = result_chunk_grid(units) = min(512, ceil(units / 3)), units = chunks (xm_hi = 0) or chunk pairs: a function
 //     of (n, xm_hi != 0) alone.
 //
 //   general (any other shape): pauli_general_kernel<T>, one work item per (string, chunk of max(1024, ceil(n / 1024))
@@ -50,31 +50,22 @@
 //
 // A string with odd ny of a real tensor is exactly 0.0 and is written on the host without a launch.
 //
-// Scratch (the buffer of ctg_reduce.hip / ctg_rdm.hip, reduce_reserve): 8 m bytes of values; power-of-two route: 648
+// Scratch (the executor's d_reduce, reduce_reserve): 8 m bytes of values; power-of-two route: 648
 // bytes per pass (at most m passes), 128 KiB of partials, 4 KiB of group sums -- 2.8 MiB at most; general route: 32
 // bytes per string, 12 bytes per non-identity letter and 8 bytes per (string, chunk of at most 1024): 35 MiB at most.
 #include <algorithm>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <type_traits>
 #include <unordered_map>
-#include <vector>
 
-#include "ctg_exec_state.h"
-#include "ctg_sample_elem.h"
+#include "ctg_result_elem.h"
+#include "ctg_result_host.h"
 
 namespace ctg {
 
-constexpr int kPauliChunk = kSampleBlock;        // elements of a chunk
-constexpr int kPauliBits = 12;                   // log2(kPauliChunk)
 constexpr int kPauliPass = 32;                   // strings of a pass: one bit each in a sign word
-constexpr int kPauliMaxGrid = 512;               // workgroups of pauli_chunk_kernel
-constexpr int kPauliMinUnits = 3;                // chunks (chunk pairs) per workgroup before the grid grows
 constexpr int kPauliSumChunk = 32;               // partials per work item of pauli_gather_kernel
 constexpr int64_t kPauliGeneralChunk = 1024;     // flat indices per work item of the general route, at least
 constexpr int64_t kPauliGeneralMaxChunks = 1024; // ... and at most this many chunks per string
-static_assert(kPauliChunk == 1 << kPauliBits, "a chunk is addressed by kPauliBits bits");
 
 // What a pass of the power-of-two route needs on the device
 struct PauliPassMeta {
@@ -131,11 +122,6 @@ template <> struct PauliElem<double2> {
     }
 };
 
-// v with its sign flipped where bit 0 of `bit` is set
-__device__ __forceinline__ double pauli_signed(double v, uint32_t bit) {
-    return __hiloint2double(__double2hiint(v) ^ (int)(bit << 31), __double2loint(v));
-}
-
 template <typename T>
 __global__ __launch_bounds__(kSampleThreads, 2) void pauli_chunk_kernel(const T* __restrict__ x, int64_t n, int vec, int64_t xm,
                                                                         int64_t units, const PauliPassMeta* __restrict__ pass,
@@ -144,20 +130,16 @@ __global__ __launch_bounds__(kSampleThreads, 2) void pauli_chunk_kernel(const T*
     constexpr int P = PauliElem<T>::P;
     constexpr int V = 16 / sizeof(T);
     constexpr int LV = V == 4 ? 2 : V == 2 ? 1 : 0;
-    constexpr int G = kPauliChunk / V / kSampleThreads;
-    constexpr int kChunkBytes = kPauliChunk * (int)sizeof(T), kSumBytes = kPauliPass * 64 * 8;
+    constexpr int G = kResultChunk / V / kSampleThreads;
+    constexpr int kChunkBytes = kResultChunk * (int)sizeof(T), kSumBytes = kPauliPass * 64 * 8;
     __shared__ __attribute__((aligned(16))) unsigned char raw[kChunkBytes > kSumBytes ? kChunkBytes : kSumBytes];
     __shared__ double r2[kPauliPass * 8];
-    union Group {
-        uint4 raw;
-        T v[V];
-    };
     uint4* l4 = reinterpret_cast<uint4*>(raw);
     double* xs = reinterpret_cast<double*>(raw);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t xlo = (uint32_t)(xm & (kPauliChunk - 1));
-    const int64_t xhi = xm >> kPauliBits;
+    const uint32_t xlo = (uint32_t)(xm & (kResultChunk - 1));
+    const int64_t xhi = xm >> kResultChunkBits;
     const uint32_t xin = xlo & (V - 1), xg = xlo >> LV;
     const bool use_lds = xg != 0;
     // xm_hi = 0, xm != 0: of the pair {e, e ^ xm_lo} the member whose lowest set bit of xm_lo is clear is summed
@@ -172,7 +154,7 @@ __global__ __launch_bounds__(kSampleThreads, 2) void pauli_chunk_kernel(const T*
 #pragma unroll
     for (int i = 0; i < G * V; ++i) es[i] = 0;
     for (int s = 0; s < count; ++s) {
-        const uint32_t z = (uint32_t)(pass->zm[s] & (kPauliChunk - 1));
+        const uint32_t z = (uint32_t)(pass->zm[s] & (kResultChunk - 1));
 #pragma unroll
         for (int g = 0; g < G; ++g)
 #pragma unroll
@@ -190,13 +172,13 @@ __global__ __launch_bounds__(kSampleThreads, 2) void pauli_chunk_kernel(const T*
     auto chunk_of = [&](int64_t q) { return xhi ? (((q >> lb) << (lb + 1)) | (q & (((int64_t)1 << lb) - 1))) : q; };
     // (loading the next unit's chunk while this one is summed was measured slower than leaving the overlap to the
     // second workgroup of the CU)
-    Group st[G];
+    Group<T> st[G];
     // ODD: some string of the pass has an odd number of Y and takes the imaginary component (never for xm = 0)
     auto sum_units = [&](auto odd_tag) {
         constexpr bool ODD = decltype(odd_tag)::value;
         for (int64_t q = blockIdx.x; q < units; q += gridDim.x) {
             const int64_t c = chunk_of(q);
-            const int64_t base = c << kPauliBits, base2 = (c ^ xhi) << kPauliBits;
+            const int64_t base = c << kResultChunkBits, base2 = (c ^ xhi) << kResultChunkBits;
             // the chunk's sign word: lane s holds parity(base & zm_s); wave-uniform
             const uint32_t cw = (uint32_t)__ballot(__popcll((unsigned long long)(base & myzm)) & 1);
 #pragma unroll
@@ -206,7 +188,7 @@ __global__ __launch_bounds__(kSampleThreads, 2) void pauli_chunk_kernel(const T*
                 if (xhi) {
 #pragma unroll
                     for (int g = 0; g < G; ++g) {
-                        Group t;
+                        Group<T> t;
                         load_group<T>(x, base2 + (int64_t)(g * kSampleThreads + tid) * V, n, vec != 0, t.v);
                         l4[g * kSampleThreads + tid] = t.raw;
                     }
@@ -218,7 +200,7 @@ __global__ __launch_bounds__(kSampleThreads, 2) void pauli_chunk_kernel(const T*
             }
 #pragma unroll
             for (int g = 0; g < G; ++g) {
-                Group pg;
+                Group<T> pg;
                 if (use_lds)
                     pg.raw = l4[(uint32_t)(g * kSampleThreads + tid) ^ xg];
                 else if (xhi)
@@ -227,12 +209,12 @@ __global__ __launch_bounds__(kSampleThreads, 2) void pauli_chunk_kernel(const T*
                     pg = st[g];
                 // the partner inside the group: element k ^ xin
                 if (V >= 2 && (xin & 1u)) {
-                    Group t = pg;
+                    Group<T> t = pg;
 #pragma unroll
                     for (int k = 0; k < V; ++k) pg.v[k] = t.v[k ^ (V >= 2 ? 1 : 0)];
                 }
                 if (V >= 4 && (xin & 2u)) {
-                    Group t = pg;
+                    Group<T> t = pg;
 #pragma unroll
                     for (int k = 0; k < V; ++k) pg.v[k] = t.v[k ^ (V >= 4 ? 2 : 0)];
                 }
@@ -245,7 +227,7 @@ __global__ __launch_bounds__(kSampleThreads, 2) void pauli_chunk_kernel(const T*
                     const uint32_t w = es[g * V + k] ^ cw;
                     // the component's own sign goes into the word: bit s of wr is the sign of string s's term, which
                     // then replaces the sign bit -- a shift, a bit-field insert and the addition per string
-                    // (the same bits as pauli_signed(re, w >> s), which the passes with a choice of component use)
+                    // (the same bits as signed_by(re, w >> s), which the passes with a choice of component use)
                     const int rh = __double2hiint(re), rl = __double2loint(re);
                     const uint32_t wr = w ^ (uint32_t)(rh >> 31);
 #pragma unroll
@@ -255,7 +237,7 @@ __global__ __launch_bounds__(kSampleThreads, 2) void pauli_chunk_kernel(const T*
                         // nobody reads
                         if ((s & (s - 1)) == 0 && s >= count) break;
                         if (ODD) {
-                            acc[s] = acc[s] + pauli_signed(((odd >> s) & 1u) ? im : re, w >> s);
+                            acc[s] = acc[s] + signed_by(((odd >> s) & 1u) ? im : re, w >> s);
                         } else {
                             const uint32_t t = wr << (31 - s);
                             acc[s] = acc[s] + __hiloint2double((int)((t & 0x80000000u) | ((uint32_t)rh & 0x7fffffffu)), rl);
@@ -342,7 +324,7 @@ __global__ __launch_bounds__(kSampleThreads) void pauli_general_kernel(const T* 
         }
         double re, im;
         PauliElem<T>::term(x[p], x[j], re, im);
-        const double v = pauli_signed(st.odd ? im : re, sign);
+        const double v = signed_by(st.odd ? im : re, sign);
         sum = j == j0 ? v : sum + v;
     }
     B[g] = sum;
@@ -364,32 +346,6 @@ using namespace ctg;
 
 namespace {
 
-int pfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    ctg_set_error_(buf);
-    return code;
-}
-
-#define HIP_TRY_P(expr)                                                                                    \
-    do {                                                                                                   \
-        hipError_t _e = (expr);                                                                            \
-        if (_e != hipSuccess)                                                                              \
-            return pfail(_e == hipErrorOutOfMemory ? CTG_E_NOMEM : CTG_E_HIP, "%s failed: %s", #expr,      \
-                         hipGetErrorString(_e));                                                           \
-    } while (0)
-
-#define LAUNCH_CHECK_P(name)                                                                               \
-    do {                                                                                                   \
-        hipError_t _e = hipGetLastError();                                                                 \
-        if (_e != hipSuccess) return pfail(CTG_E_HIP, name " launch failed: %s", hipGetErrorString(_e));   \
-    } while (0)
-
-int64_t up256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
 double pauli_factor(int ny, bool halved) {
     const double f = (((ny + 1) / 2) & 1) ? -1.0 : 1.0;   // (-1)^ceil(ny / 2)
     return halved ? 2.0 * f : f;
@@ -400,28 +356,19 @@ template <typename T>
 int pauli_pass_launch(ctg_exec* e, int64_t n, int64_t xm, const PauliPassMeta* d_pass, double* part, double* B, double* d_out) {
     hipStream_t st = e->stream;
     const int vec = ((uintptr_t)e->d_result & 15) == 0 ? 1 : 0;
-    const int64_t nchunks = n / kPauliChunk;
-    const int64_t units = (xm >> kPauliBits) ? nchunks / 2 : nchunks;
-    const int grid = (int)std::min<int64_t>(kPauliMaxGrid, (units + kPauliMinUnits - 1) / kPauliMinUnits);
+    const int64_t nchunks = n / kResultChunk;
+    const int64_t units = (xm >> kResultChunkBits) ? nchunks / 2 : nchunks;
+    const int grid = result_chunk_grid(units);
     const int ngroups = (grid + kPauliSumChunk - 1) / kPauliSumChunk;
     pauli_chunk_kernel<T><<<dim3((unsigned)grid), dim3(kSampleThreads), 0, st>>>((const T*)e->d_result, n, vec, xm, units, d_pass, part);
-    LAUNCH_CHECK_P("pauli_chunk_kernel");
+    LAUNCH_CHECK("pauli_chunk_kernel");
     const int total = ngroups * kPauliPass;
     pauli_gather_kernel<<<dim3((unsigned)((total + kSampleThreads - 1) / kSampleThreads)), dim3(kSampleThreads), 0, st>>>(part, grid,
                                                                                                                         total, B);
-    LAUNCH_CHECK_P("pauli_gather_kernel");
+    LAUNCH_CHECK("pauli_gather_kernel");
     pauli_finish_kernel<<<dim3(1), dim3(64), 0, st>>>(B, ngroups, d_pass, d_out);
-    LAUNCH_CHECK_P("pauli_finish_kernel");
+    LAUNCH_CHECK("pauli_finish_kernel");
     return CTG_OK;
-}
-
-int pauli_pass(ctg_exec* e, int64_t n, int64_t xm, const PauliPassMeta* d_pass, double* part, double* B, double* d_out) {
-    switch (e->plan->dtype) {
-        case CTG_F32: return pauli_pass_launch<float>(e, n, xm, d_pass, part, B, d_out);
-        case CTG_F64: return pauli_pass_launch<double>(e, n, xm, d_pass, part, B, d_out);
-        case CTG_C64: return pauli_pass_launch<float2>(e, n, xm, d_pass, part, B, d_out);
-        default: return pauli_pass_launch<double2>(e, n, xm, d_pass, part, B, d_out);
-    }
 }
 
 template <typename T>
@@ -431,10 +378,10 @@ int pauli_general_launch(ctg_exec* e, int64_t n, const PauliGenString* d_strs, c
     const int64_t total = (int64_t)ns * nch;
     pauli_general_kernel<T><<<dim3((unsigned)((total + kSampleThreads - 1) / kSampleThreads)), dim3(kSampleThreads), 0, st>>>(
         (const T*)e->d_result, n, d_strs, d_stride, d_kind, ns, chunk, total, B);
-    LAUNCH_CHECK_P("pauli_general_kernel");
+    LAUNCH_CHECK("pauli_general_kernel");
     pauli_general_finish_kernel<<<dim3((unsigned)((ns + kSampleThreads - 1) / kSampleThreads)), dim3(kSampleThreads), 0, st>>>(
         B, ns, nch, d_strs, d_out);
-    LAUNCH_CHECK_P("pauli_general_finish_kernel");
+    LAUNCH_CHECK("pauli_general_finish_kernel");
     return CTG_OK;
 }
 
@@ -442,47 +389,28 @@ int pauli_general_launch(ctg_exec* e, int64_t n, const PauliGenString* d_strs, c
 
 extern "C" int ctg_exec_result_pauli(ctg_exec* e, int64_t rank, const int64_t* extents, int64_t m, const uint8_t* ops,
                                      double* out) {
-    if (!e || !extents || !ops || !out) return pfail(CTG_E_INVALID, "pauli: null argument");
-    if (rank < 0) return pfail(CTG_E_INVALID, "pauli: negative rank");
-    int64_t n = 1;
-    bool pow2 = true;
-    for (int64_t a = 0; a < rank; ++a) {
-        if (extents[a] < 1) return pfail(CTG_E_INVALID, "pauli: an extent is not positive");
-        if (extents[a] > kReduceMaxElems / n) return pfail(CTG_E_INVALID, "pauli: the extents' product does not equal result_elems");
-        n *= extents[a];
-        pow2 = pow2 && (extents[a] & (extents[a] - 1)) == 0;
-    }
-    if (n != e->plan->result_elems) return pfail(CTG_E_INVALID, "pauli: the extents' product does not equal result_elems");
+    if (!e || !extents || !ops || !out) return result_fail(CTG_E_INVALID, "pauli: null argument");
+    ResultShape shape;
+    const char* why = "";
+    if (result_shape(rank, extents, e->plan->result_elems, &shape, &why) != CTG_OK) return result_fail(CTG_E_INVALID, "pauli: %s", why);
+    const int64_t n = shape.n;
+    const std::vector<int64_t>& stride = shape.strides;
     if (m < 0 || m > CTG_PAULI_MAX_STRINGS)
-        return pfail(CTG_E_INVALID, "pauli: %lld strings; between 0 and CTG_PAULI_MAX_STRINGS = %d", (long long)m,
+        return result_fail(CTG_E_INVALID, "pauli: %lld strings; between 0 and CTG_PAULI_MAX_STRINGS = %d", (long long)m,
                      CTG_PAULI_MAX_STRINGS);
     for (int64_t s = 0; s < m; ++s)
         for (int64_t a = 0; a < rank; ++a) {
             const uint8_t op = ops[s * rank + a];
-            if (op > 3) return pfail(CTG_E_INVALID, "pauli: string %lld, axis %lld: code %d is none of 0 .. 3", (long long)s, (long long)a, (int)op);
+            if (op > 3) return result_fail(CTG_E_INVALID, "pauli: string %lld, axis %lld: code %d is none of 0 .. 3", (long long)s, (long long)a, (int)op);
             if (op != 0 && extents[a] != 2)
-                return pfail(CTG_E_INVALID, "pauli: string %lld puts a letter other than I on axis %lld of extent %lld", (long long)s,
+                return result_fail(CTG_E_INVALID, "pauli: string %lld puts a letter other than I on axis %lld of extent %lld", (long long)s,
                              (long long)a, (long long)extents[a]);
         }
     if (m == 0) return CTG_OK;
-    {
-        // sum p of the result by the statistics passes of ctg_sample.hip (synchronises)
-        double sum_p = 0.0;
-        const int rc = ctg_exec_result_stats(e, &sum_p, nullptr, nullptr, nullptr);
-        if (rc != CTG_OK) return rc;
-        if (!std::isfinite(sum_p))
-            return pfail(CTG_E_NORM, "the result tensor's sum of |x|^2 is %g: no expectation values of it", sum_p);
-    }
+    int rc = result_norm_finite(e, "no expectation values of it");
+    if (rc != CTG_OK) return rc;
     const int dtype = e->plan->dtype;
     const bool real = dtype == CTG_F32 || dtype == CTG_F64;
-    std::vector<int64_t> stride((size_t)rank);
-    {
-        int64_t s = 1;
-        for (int64_t a = rank - 1; a >= 0; --a) {
-            stride[a] = s;
-            s *= extents[a];
-        }
-    }
     // a string of a real tensor with an odd number of Y is exactly zero: no launch
     std::vector<int> ny((size_t)m, 0);
     std::vector<char> launched((size_t)m, 1);
@@ -498,8 +426,7 @@ extern "C" int ctg_exec_result_pauli(ctg_exec* e, int64_t rank, const int64_t* e
         for (int64_t s = 0; s < m; ++s) out[s] = 0.0;
         return CTG_OK;
     }
-    const bool fast = pow2 && n >= kPauliChunk;
-    if (fast) {
+    if (shape.pow2 && n >= kResultChunk) {
         // groups by xm in order of first appearance, the caller's order inside; passes of at most kPauliPass
         std::vector<int64_t> gx;
         std::vector<std::vector<int64_t>> members;
@@ -539,23 +466,28 @@ extern "C" int ctg_exec_result_pauli(ctg_exec* e, int64_t rank, const int64_t* e
             }
         // [values: m | the passes | partials of the workgroups | sums of groups of partials]
         const int64_t pass_bytes = (int64_t)passes.size() * (int64_t)sizeof(PauliPassMeta);
-        const int64_t part_bytes = (int64_t)kPauliMaxGrid * kPauliPass * 8;
-        const int64_t b_bytes = (int64_t)((kPauliMaxGrid + kPauliSumChunk - 1) / kPauliSumChunk) * kPauliPass * 8;
-        {
-            const int rc = reduce_reserve(e, up256(out_bytes) + up256(pass_bytes) + up256(part_bytes) + up256(b_bytes));
-            if (rc != CTG_OK) return rc;
-        }
-        double* d_out = (double*)e->d_reduce;
-        PauliPassMeta* d_pass = (PauliPassMeta*)((char*)e->d_reduce + up256(out_bytes));
-        double* part = (double*)((char*)d_pass + up256(pass_bytes));
-        double* B = (double*)((char*)part + up256(part_bytes));
-        HIP_TRY_P(hipMemcpyAsync(d_pass, passes.data(), (size_t)pass_bytes, hipMemcpyHostToDevice, e->stream));
+        const int64_t part_bytes = (int64_t)kResultMaxGrid * kPauliPass * 8;
+        const int64_t b_bytes = (int64_t)((kResultMaxGrid + kPauliSumChunk - 1) / kPauliSumChunk) * kPauliPass * 8;
+        double *d_out = nullptr, *part = nullptr, *B = nullptr;
+        PauliPassMeta* d_pass = nullptr;
+        auto lay = [&](void* base) {
+            Carve c(base);
+            d_out = c.take<double>(out_bytes);
+            d_pass = c.take<PauliPassMeta>(pass_bytes);
+            part = c.take<double>(part_bytes);
+            B = c.take<double>(b_bytes);
+            return c.bytes();
+        };
+        rc = reduce_reserve(e, lay(nullptr));
+        if (rc != CTG_OK) return rc;
+        lay(e->d_reduce);
+        HIP_TRY(hipMemcpyAsync(d_pass, passes.data(), (size_t)pass_bytes, hipMemcpyHostToDevice, e->stream));
         for (size_t p = 0; p < passes.size(); ++p) {
-            const int rc = pauli_pass(e, n, pass_xm[p], d_pass + p, part, B, d_out);
+            rc = dispatch_elem(dtype, [&](auto t) { return pauli_pass_launch<decltype(t)>(e, n, pass_xm[p], d_pass + p, part, B, d_out); });
             if (rc != CTG_OK) return rc;
         }
-        HIP_TRY_P(hipMemcpyAsync(values.data(), d_out, (size_t)out_bytes, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY_P(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipMemcpyAsync(values.data(), d_out, (size_t)out_bytes, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
     } else {
         std::vector<PauliGenString> strs;
         std::vector<int64_t> ax_stride;
@@ -583,30 +515,31 @@ extern "C" int ctg_exec_result_pauli(ctg_exec* e, int64_t rank, const int64_t* e
         const int64_t str_bytes = (int64_t)ns * (int64_t)sizeof(PauliGenString);
         const int64_t sa_bytes = (int64_t)ax_stride.size() * 8, ka_bytes = (int64_t)ax_kind.size() * 4;
         const int64_t b_bytes = (int64_t)ns * nch * 8;
-        {
-            const int rc = reduce_reserve(e, up256(out_bytes) + up256(str_bytes) + up256(sa_bytes) + up256(ka_bytes) + up256(b_bytes));
-            if (rc != CTG_OK) return rc;
-        }
-        double* d_out = (double*)e->d_reduce;
-        PauliGenString* d_strs = (PauliGenString*)((char*)e->d_reduce + up256(out_bytes));
-        int64_t* d_stride = (int64_t*)((char*)d_strs + up256(str_bytes));
-        int32_t* d_kind = (int32_t*)((char*)d_stride + up256(sa_bytes));
-        double* B = (double*)((char*)d_kind + up256(ka_bytes));
-        HIP_TRY_P(hipMemcpyAsync(d_strs, strs.data(), (size_t)str_bytes, hipMemcpyHostToDevice, e->stream));
-        if (sa_bytes) {
-            HIP_TRY_P(hipMemcpyAsync(d_stride, ax_stride.data(), (size_t)sa_bytes, hipMemcpyHostToDevice, e->stream));
-            HIP_TRY_P(hipMemcpyAsync(d_kind, ax_kind.data(), (size_t)ka_bytes, hipMemcpyHostToDevice, e->stream));
-        }
-        int rc;
-        switch (dtype) {
-            case CTG_F32: rc = pauli_general_launch<float>(e, n, d_strs, d_stride, d_kind, ns, chunk, nch, B, d_out); break;
-            case CTG_F64: rc = pauli_general_launch<double>(e, n, d_strs, d_stride, d_kind, ns, chunk, nch, B, d_out); break;
-            case CTG_C64: rc = pauli_general_launch<float2>(e, n, d_strs, d_stride, d_kind, ns, chunk, nch, B, d_out); break;
-            default: rc = pauli_general_launch<double2>(e, n, d_strs, d_stride, d_kind, ns, chunk, nch, B, d_out); break;
-        }
+        double *d_out = nullptr, *B = nullptr;
+        PauliGenString* d_strs = nullptr;
+        int64_t* d_stride = nullptr;
+        int32_t* d_kind = nullptr;
+        auto lay = [&](void* base) {
+            Carve c(base);
+            d_out = c.take<double>(out_bytes);
+            d_strs = c.take<PauliGenString>(str_bytes);
+            d_stride = c.take<int64_t>(sa_bytes);
+            d_kind = c.take<int32_t>(ka_bytes);
+            B = c.take<double>(b_bytes);
+            return c.bytes();
+        };
+        rc = reduce_reserve(e, lay(nullptr));
         if (rc != CTG_OK) return rc;
-        HIP_TRY_P(hipMemcpyAsync(values.data(), d_out, (size_t)out_bytes, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY_P(hipStreamSynchronize(e->stream));
+        lay(e->d_reduce);
+        HIP_TRY(hipMemcpyAsync(d_strs, strs.data(), (size_t)str_bytes, hipMemcpyHostToDevice, e->stream));
+        if (sa_bytes) {
+            HIP_TRY(hipMemcpyAsync(d_stride, ax_stride.data(), (size_t)sa_bytes, hipMemcpyHostToDevice, e->stream));
+            HIP_TRY(hipMemcpyAsync(d_kind, ax_kind.data(), (size_t)ka_bytes, hipMemcpyHostToDevice, e->stream));
+        }
+        rc = dispatch_elem(dtype, [&](auto t) { return pauli_general_launch<decltype(t)>(e, n, d_strs, d_stride, d_kind, ns, chunk, nch, B, d_out); });
+        if (rc != CTG_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(values.data(), d_out, (size_t)out_bytes, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
     }
     for (int64_t s = 0; s < m; ++s) out[s] = launched[s] ? values[s] : 0.0;
     return CTG_OK;

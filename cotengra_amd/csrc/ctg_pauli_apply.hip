@@ -22,7 +22,7 @@
 // No atomics; no sum crosses a thread: the bits of y are a function of (dtype, extents, ops in order, coeffs, the
 // tensor's bytes) alone.
 //
-//   power of two (every extent a power of two, at least kApplyChunk = 4096 elements):
+//   power of two (every extent a power of two, at least kResultChunk = 4096 elements):
 //
 //     pauli_apply_kernel<T>   256 threads, two workgroups per CU; one launch.  A workgroup owns the output chunks wg,
 //                             wg + grid, ... of 4096 elements; thread t holds the 16-byte groups g 256 + t of a chunk
@@ -45,30 +45,20 @@
 //   general (any other shape): pauli_apply_general_kernel<T>, a thread per output element (grid-stride), the same
 //   groups and order; partner and signs from the digits (j / stride) & 1 as in pauli_general_kernel.  Not tuned.
 //
-// Scratch (the buffer of ctg_reduce.hip / ctg_rdm.hip / ctg_pauli.hip, reduce_reserve): the pass metadata (1640 bytes
+// Scratch (the executor's d_reduce, reduce_reserve): the pass metadata (1640 bytes
 // per pass, at most m passes; general route: 24 bytes per group, 24 per string, 8 per non-identity letter) and, when
 // only host_out is given, result_elems elements of y.
 #include <algorithm>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 #include <string>
 #include <unordered_map>
-#include <vector>
 
-#include "ctg_exec_state.h"
-#include "ctg_sample_elem.h"
+#include "ctg_result_elem.h"
+#include "ctg_result_host.h"
 
 namespace ctg {
 
-constexpr int kApplyChunk = kSampleBlock;   // elements of a chunk
-constexpr int kApplyBits = 12;              // log2(kApplyChunk)
 constexpr int kApplyPass = 32;              // strings of a pass: one bit each in a sign word
-constexpr int kApplyMaxGrid = 512;          // workgroups of pauli_apply_kernel
-constexpr int kApplyMinChunks = 3;          // chunks per workgroup before the grid grows
 constexpr int64_t kApplyGeneralMaxBlocks = 1 << 20;
-static_assert(kApplyChunk == 1 << kApplyBits, "a chunk is addressed by kApplyBits bits");
 
 // What a pass of the power-of-two route needs on the device
 struct ApplyPassMeta {
@@ -95,50 +85,7 @@ struct ApplyGenString {
     double coef;        // (-i)^ny c_s without the i: the signed real factor
 };
 
-// acc += W p, rounded as the header defines; the rounding of acc to T
-template <typename T> struct ApplyElem;
-template <> struct ApplyElem<float> {
-    static constexpr int P = 1;
-    static __device__ __forceinline__ void mac(float p, double wre, double, double& are, double&) {
-#pragma clang fp contract(off)
-        const double a = wre * (double)p;
-        are = are + a;
-    }
-    static __device__ __forceinline__ float round(double are, double) { return (float)are; }
-};
-template <> struct ApplyElem<double> {
-    static constexpr int P = 1;
-    static __device__ __forceinline__ void mac(double p, double wre, double, double& are, double&) {
-#pragma clang fp contract(off)
-        const double a = wre * p;
-        are = are + a;
-    }
-    static __device__ __forceinline__ double round(double are, double) { return are; }
-};
-template <> struct ApplyElem<float2> {
-    static constexpr int P = 2;
-    static __device__ __forceinline__ void mac(float2 p, double wre, double wim, double& are, double& aim) {
-#pragma clang fp contract(off)
-        const double pr = (double)p.x, pi = (double)p.y;
-        const double a = wre * pr, b = wim * pi, c = wre * pi, d = wim * pr;
-        const double tr = a - b, ti = c + d;
-        are = are + tr;
-        aim = aim + ti;
-    }
-    static __device__ __forceinline__ float2 round(double are, double aim) { return make_float2((float)are, (float)aim); }
-};
-template <> struct ApplyElem<double2> {
-    static constexpr int P = 2;
-    static __device__ __forceinline__ void mac(double2 p, double wre, double wim, double& are, double& aim) {
-#pragma clang fp contract(off)
-        const double a = wre * p.x, b = wim * p.y, c = wre * p.y, d = wim * p.x;
-        const double tr = a - b, ti = c + d;
-        are = are + tr;
-        aim = aim + ti;
-    }
-    static __device__ __forceinline__ double2 round(double are, double aim) { return make_double2(are, aim); }
-};
-
+// (acc += W p and the rounding of acc to T: ApplyElem<T> of ctg_result_elem.h)
 template <typename T>
 __global__ __launch_bounds__(kSampleThreads, 2) void pauli_apply_kernel(const T* __restrict__ x, int64_t n, int vec, int vec_out,
                                                                         int64_t nchunks, const ApplyPassMeta* __restrict__ pass,
@@ -147,19 +94,15 @@ __global__ __launch_bounds__(kSampleThreads, 2) void pauli_apply_kernel(const T*
     constexpr int P = ApplyElem<T>::P;
     constexpr int V = 16 / sizeof(T);
     constexpr int LV = V == 4 ? 2 : V == 2 ? 1 : 0;
-    constexpr int G = kApplyChunk / V / kSampleThreads;
+    constexpr int G = kResultChunk / V / kSampleThreads;
     constexpr int E = G * V;   // elements of a thread: 16
     static_assert(G <= 16 && V <= 4, "gw and kw of ApplyPassMeta");
-    __shared__ __attribute__((aligned(16))) unsigned char raw[kApplyChunk * (int)sizeof(T)];
-    union Group {
-        uint4 raw;
-        T v[V];
-    };
+    __shared__ __attribute__((aligned(16))) unsigned char raw[kResultChunk * (int)sizeof(T)];
     uint4* l4 = reinterpret_cast<uint4*>(raw);
     const int tid = threadIdx.x, lane = tid & 63;
 
     for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        const int64_t base = c << kApplyBits;
+        const int64_t base = c << kResultChunkBits;
         double acc_re[E], acc_im[P == 2 ? E : 1], w_re[E], w_im[P == 2 ? E : 1];
 #pragma unroll
         for (int i = 0; i < E; ++i) {
@@ -200,14 +143,14 @@ __global__ __launch_bounds__(kSampleThreads, 2) void pauli_apply_kernel(const T*
             if (!pm->last) continue;
             // the group's weights are complete: multiply the partner in
             const int64_t xm = pm->xm;
-            const uint32_t xlo = (uint32_t)(xm & (kApplyChunk - 1));
-            const int64_t base2 = (c ^ (xm >> kApplyBits)) << kApplyBits;
+            const uint32_t xlo = (uint32_t)(xm & (kResultChunk - 1));
+            const int64_t base2 = (c ^ (xm >> kResultChunkBits)) << kResultChunkBits;
             const uint32_t xin = xlo & (V - 1), xg = xlo >> LV;
             if (xg) {
                 __syncthreads();   // (the group before has read the copy)
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
-                    Group t;
+                    Group<T> t;
                     load_group<T>(x, base2 + (int64_t)(g * kSampleThreads + tid) * V, n, vec != 0, t.v);
                     l4[g * kSampleThreads + tid] = t.raw;
                 }
@@ -215,19 +158,19 @@ __global__ __launch_bounds__(kSampleThreads, 2) void pauli_apply_kernel(const T*
             }
 #pragma unroll
             for (int g = 0; g < G; ++g) {
-                Group pg;
+                Group<T> pg;
                 if (xg)
                     pg.raw = l4[(uint32_t)(g * kSampleThreads + tid) ^ xg];
                 else
                     load_group<T>(x, base2 + (int64_t)(g * kSampleThreads + tid) * V, n, vec != 0, pg.v);
                 // the partner inside the group: element k ^ xin
                 if (V >= 2 && (xin & 1u)) {
-                    Group t = pg;
+                    Group<T> t = pg;
 #pragma unroll
                     for (int k = 0; k < V; ++k) pg.v[k] = t.v[k ^ (V >= 2 ? 1 : 0)];
                 }
                 if (V >= 4 && (xin & 2u)) {
-                    Group t = pg;
+                    Group<T> t = pg;
 #pragma unroll
                     for (int k = 0; k < V; ++k) pg.v[k] = t.v[k ^ (V >= 4 ? 2 : 0)];
                 }
@@ -242,7 +185,7 @@ __global__ __launch_bounds__(kSampleThreads, 2) void pauli_apply_kernel(const T*
         }
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-            Group o;
+            Group<T> o;
 #pragma unroll
             for (int k = 0; k < V; ++k) o.v[k] = ApplyElem<T>::round(acc_re[g * V + k], acc_im[P == 2 ? g * V + k : 0]);
             const int64_t e = base + (int64_t)(g * kSampleThreads + tid) * V;   // (e + V <= n: n is a multiple of 4096)
@@ -254,11 +197,6 @@ __global__ __launch_bounds__(kSampleThreads, 2) void pauli_apply_kernel(const T*
             }
         }
     }
-}
-
-// v with its sign flipped where bit 0 of `bit` is set
-__device__ __forceinline__ double apply_signed(double v, uint32_t bit) {
-    return __hiloint2double(__double2hiint(v) ^ (int)(bit << 31), __double2loint(v));
 }
 
 template <typename T>
@@ -282,7 +220,7 @@ __global__ __launch_bounds__(kSampleThreads) void pauli_apply_general_kernel(con
                 const ApplyGenString st = strs[s];
                 uint32_t sign = 0;
                 for (int a = 0; a < st.nz; ++a) sign ^= (uint32_t)((j / zstride[st.zax0 + a]) & 1);   // Z, Y: the digit's parity
-                const double v = apply_signed(st.coef, sign);
+                const double v = signed_by(st.coef, sign);
                 if (st.odd)
                     wim = wim + v;
                 else
@@ -300,38 +238,6 @@ using namespace ctg;
 
 namespace {
 
-int afail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    ctg_set_error_(buf);
-    return code;
-}
-
-#define HIP_TRY_A(expr)                                                                                    \
-    do {                                                                                                   \
-        hipError_t _e = (expr);                                                                            \
-        if (_e != hipSuccess)                                                                              \
-            return afail(_e == hipErrorOutOfMemory ? CTG_E_NOMEM : CTG_E_HIP, "%s failed: %s", #expr,      \
-                         hipGetErrorString(_e));                                                           \
-    } while (0)
-
-#define LAUNCH_CHECK_A(name)                                                                               \
-    do {                                                                                                   \
-        hipError_t _e = hipGetLastError();                                                                 \
-        if (_e != hipSuccess) return afail(CTG_E_HIP, name " launch failed: %s", hipGetErrorString(_e));   \
-    } while (0)
-
-int64_t up256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
-// host -> device from a vector of the caller's frame, complete on return: no copy outlives the frame, on any path
-hipError_t upload(void* dst, const void* src, int64_t bytes, hipStream_t st) {
-    const hipError_t e = hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, st);
-    return e != hipSuccess ? e : hipStreamSynchronize(st);
-}
-
 uint32_t parity64(int64_t v) { return (uint32_t)(__builtin_popcountll((unsigned long long)v) & 1); }
 
 // (-i)^ny c: the signed real factor (the component is chosen by ny & 1)
@@ -341,11 +247,10 @@ template <typename T>
 int apply_fast_launch(ctg_exec* e, int64_t n, const ApplyPassMeta* d_pass, int npass, void* y) {
     const int vec = ((uintptr_t)e->d_result & 15) == 0 ? 1 : 0;
     const int vec_out = ((uintptr_t)y & 15) == 0 ? 1 : 0;
-    const int64_t nchunks = n / kApplyChunk;
-    const int grid = (int)std::min<int64_t>(kApplyMaxGrid, (nchunks + kApplyMinChunks - 1) / kApplyMinChunks);
-    pauli_apply_kernel<T><<<dim3((unsigned)grid), dim3(kSampleThreads), 0, e->stream>>>((const T*)e->d_result, n, vec, vec_out, nchunks,
+    const int64_t nchunks = n / kResultChunk;
+    pauli_apply_kernel<T><<<dim3((unsigned)result_chunk_grid(nchunks)), dim3(kSampleThreads), 0, e->stream>>>((const T*)e->d_result, n, vec, vec_out, nchunks,
                                                                                          d_pass, npass, (T*)y);
-    LAUNCH_CHECK_A("pauli_apply_kernel");
+    LAUNCH_CHECK("pauli_apply_kernel");
     return CTG_OK;
 }
 
@@ -355,7 +260,7 @@ int apply_general_launch(ctg_exec* e, int64_t n, const ApplyGenGroup* d_groups, 
     const int64_t blocks = std::min<int64_t>(kApplyGeneralMaxBlocks, (n + kSampleThreads - 1) / kSampleThreads);
     pauli_apply_general_kernel<T><<<dim3((unsigned)blocks), dim3(kSampleThreads), 0, e->stream>>>((const T*)e->d_result, n, d_groups,
                                                                                                    ngroups, d_strs, d_xs, d_zs, (T*)y);
-    LAUNCH_CHECK_A("pauli_apply_general_kernel");
+    LAUNCH_CHECK("pauli_apply_general_kernel");
     return CTG_OK;
 }
 
@@ -363,70 +268,44 @@ int apply_general_launch(ctg_exec* e, int64_t n, const ApplyGenGroup* d_groups, 
 
 extern "C" int ctg_exec_result_pauli_apply(ctg_exec* e, int64_t rank, const int64_t* extents, int64_t m, const uint8_t* ops,
                                            const double* coeffs, void* dev_out, void* host_out) {
-    if (!e || !extents || !ops) return afail(CTG_E_INVALID, "pauli_apply: null argument");
-    if (!dev_out && !host_out) return afail(CTG_E_INVALID, "pauli_apply: neither dev_out nor host_out is given");
-    if (rank < 0) return afail(CTG_E_INVALID, "pauli_apply: negative rank");
-    int64_t n = 1;
-    bool pow2 = true;
-    for (int64_t a = 0; a < rank; ++a) {
-        if (extents[a] < 1) return afail(CTG_E_INVALID, "pauli_apply: an extent is not positive");
-        if (extents[a] > kReduceMaxElems / n)
-            return afail(CTG_E_INVALID, "pauli_apply: the extents' product does not equal result_elems");
-        n *= extents[a];
-        pow2 = pow2 && (extents[a] & (extents[a] - 1)) == 0;
-    }
-    if (n != e->plan->result_elems) return afail(CTG_E_INVALID, "pauli_apply: the extents' product does not equal result_elems");
+    if (!e || !extents || !ops) return result_fail(CTG_E_INVALID, "pauli_apply: null argument");
+    ApplyOut out{"pauli_apply", dev_out, host_out};
+    if (out.given() != CTG_OK) return CTG_E_INVALID;
+    ResultShape shape;
+    const char* why = "";
+    if (result_shape(rank, extents, e->plan->result_elems, &shape, &why) != CTG_OK)
+        return result_fail(CTG_E_INVALID, "pauli_apply: %s", why);
+    const int64_t n = shape.n;
+    const std::vector<int64_t>& stride = shape.strides;
     if (m < 0 || m > CTG_PAULI_MAX_STRINGS)
-        return afail(CTG_E_INVALID, "pauli_apply: %lld strings; between 0 and CTG_PAULI_MAX_STRINGS = %d", (long long)m,
+        return result_fail(CTG_E_INVALID, "pauli_apply: %lld strings; between 0 and CTG_PAULI_MAX_STRINGS = %d", (long long)m,
                      CTG_PAULI_MAX_STRINGS);
-    if (m > 0 && !coeffs) return afail(CTG_E_INVALID, "pauli_apply: null coeffs");
+    if (m > 0 && !coeffs) return result_fail(CTG_E_INVALID, "pauli_apply: null coeffs");
     const int dtype = e->plan->dtype;
     const bool real = dtype == CTG_F32 || dtype == CTG_F64;
-    const int64_t item = ctg_item_size(dtype), bytes = n * item;
-    if (dev_out) {
-        const uintptr_t d0 = (uintptr_t)dev_out, r0 = (uintptr_t)e->d_result;
-        if (d0 < r0 + (uintptr_t)bytes && r0 < d0 + (uintptr_t)bytes)
-            return afail(CTG_E_INVALID, "pauli_apply: dev_out overlaps the result tensor");
-    }
+    const int64_t item = ctg_item_size(dtype);
+    if (out.overlap(e, n * item) != CTG_OK) return CTG_E_INVALID;
     std::vector<int> ny((size_t)m, 0);
     for (int64_t s = 0; s < m; ++s) {
         for (int64_t a = 0; a < rank; ++a) {
             const uint8_t op = ops[s * rank + a];
             if (op > 3)
-                return afail(CTG_E_INVALID, "pauli_apply: string %lld, axis %lld: code %d is none of 0 .. 3", (long long)s, (long long)a,
+                return result_fail(CTG_E_INVALID, "pauli_apply: string %lld, axis %lld: code %d is none of 0 .. 3", (long long)s, (long long)a,
                              (int)op);
             if (op != 0 && extents[a] != 2)
-                return afail(CTG_E_INVALID, "pauli_apply: string %lld puts a letter other than I on axis %lld of extent %lld",
+                return result_fail(CTG_E_INVALID, "pauli_apply: string %lld puts a letter other than I on axis %lld of extent %lld",
                              (long long)s, (long long)a, (long long)extents[a]);
             ny[s] += op == 2;
         }
-        if (!std::isfinite(coeffs[s])) return afail(CTG_E_INVALID, "pauli_apply: coefficient %lld is not finite", (long long)s);
+        if (!std::isfinite(coeffs[s])) return result_fail(CTG_E_INVALID, "pauli_apply: coefficient %lld is not finite", (long long)s);
         if (real && (ny[s] & 1))
-            return afail(CTG_E_INVALID, "pauli_apply: string %lld has an odd number of Y: P x of a real tensor is not real", (long long)s);
+            return result_fail(CTG_E_INVALID, "pauli_apply: string %lld has an odd number of Y: P x of a real tensor is not real", (long long)s);
     }
     hipStream_t st = e->stream;
-    if (m == 0) {
-        if (dev_out) {
-            HIP_TRY_A(hipMemsetAsync(dev_out, 0, (size_t)bytes, st));
-            HIP_TRY_A(hipStreamSynchronize(st));
-        }
-        if (host_out) memset(host_out, 0, (size_t)bytes);
-        return CTG_OK;
-    }
+    if (m == 0) return out.zero(st);
     {
-        // sum p of the result by the statistics passes of ctg_sample.hip (synchronises)
-        double sum_p = 0.0;
-        const int rc = ctg_exec_result_stats(e, &sum_p, nullptr, nullptr, nullptr);
+        const int rc = result_norm_finite(e, "no Pauli sum is applied to it");
         if (rc != CTG_OK) return rc;
-        if (!std::isfinite(sum_p)) return afail(CTG_E_NORM, "the result tensor's sum of |x|^2 is %g: no Pauli sum is applied to it", sum_p);
-    }
-    std::vector<int64_t> stride((size_t)rank);
-    {
-        int64_t s = 1;
-        for (int64_t a = rank - 1; a >= 0; --a) {
-            stride[a] = s;
-            s *= extents[a];
-        }
     }
     // groups by the X / Y axis set in order of first appearance, the caller's order inside
     std::vector<std::vector<int64_t>> members;
@@ -443,11 +322,10 @@ extern "C" int ctg_exec_result_pauli_apply(ctg_exec* e, int64_t rank, const int6
             members[it->second].push_back(s);
         }
     }
-    const int64_t stage_bytes = dev_out ? 0 : up256(bytes);
-    const bool fast = pow2 && n >= kApplyChunk;
-    void* y = dev_out;
-    if (fast) {
-        const int LV = item == 4 ? 2 : item == 8 ? 1 : 0, V = 1 << LV, G = kApplyChunk / V / kSampleThreads;
+    void* y = nullptr;
+    int rc;
+    if (shape.pow2 && n >= kResultChunk) {
+        const int LV = item == 4 ? 2 : item == 8 ? 1 : 0, V = 1 << LV, G = kResultChunk / V / kSampleThreads;
         std::vector<ApplyPassMeta> passes;
         for (const auto& mem : members) {
             int64_t xm = 0;
@@ -471,7 +349,7 @@ extern "C" int ctg_exec_result_pauli_apply(ctg_exec* e, int64_t rank, const int6
                     pm.zm[i] = zm;
                     pm.coef[i] = std::fabs(c);
                     if (ny[s] & 1) pm.odd |= 1u << i;
-                    const int64_t zlo = zm & (kApplyChunk - 1);
+                    const int64_t zlo = zm & (kResultChunk - 1);
                     for (int t = 0; t < kSampleThreads; ++t) pm.tw[t] |= parity64(((int64_t)t << LV) & zlo) << i;
                     for (int g = 0; g < G; ++g) pm.gw[g] |= parity64(((int64_t)g * kSampleThreads << LV) & zlo) << i;
                     for (int k = 0; k < V; ++k) pm.kw[k] |= (parity64((int64_t)k & zlo) ^ (std::signbit(c) ? 1u : 0u)) << i;
@@ -481,24 +359,19 @@ extern "C" int ctg_exec_result_pauli_apply(ctg_exec* e, int64_t rank, const int6
         }
         // [the passes | y, when it is staged for host_out]
         const int64_t pass_bytes = (int64_t)passes.size() * (int64_t)sizeof(ApplyPassMeta);
-        {
-            const int rc = reduce_reserve(e, up256(pass_bytes) + stage_bytes);
-            if (rc != CTG_OK) return rc;
-        }
-        ApplyPassMeta* d_pass = (ApplyPassMeta*)e->d_reduce;
-        if (!y) y = (char*)e->d_reduce + up256(pass_bytes);
-        HIP_TRY_A(upload(d_pass, passes.data(), pass_bytes, st));
-        int rc;
-        const int np = (int)passes.size();
-        switch (dtype) {
-            case CTG_F32: rc = apply_fast_launch<float>(e, n, d_pass, np, y); break;
-            case CTG_F64: rc = apply_fast_launch<double>(e, n, d_pass, np, y); break;
-            case CTG_C64: rc = apply_fast_launch<float2>(e, n, d_pass, np, y); break;
-            default: rc = apply_fast_launch<double2>(e, n, d_pass, np, y); break;
-        }
+        ApplyPassMeta* d_pass = nullptr;
+        auto lay = [&](void* base) {
+            Carve c(base);
+            d_pass = c.take<ApplyPassMeta>(pass_bytes);
+            y = out.y(c.take<char>(out.stage_bytes()));
+            return c.bytes();
+        };
+        rc = reduce_reserve(e, lay(nullptr));
         if (rc != CTG_OK) return rc;
-        if (host_out) HIP_TRY_A(hipMemcpyAsync(host_out, y, (size_t)bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY_A(hipStreamSynchronize(st));
+        lay(e->d_reduce);
+        HIP_TRY(upload(d_pass, passes.data(), pass_bytes, st));
+        const int np = (int)passes.size();
+        rc = dispatch_elem(dtype, [&](auto t) { return apply_fast_launch<decltype(t)>(e, n, d_pass, np, y); });
     } else {
         std::vector<ApplyGenGroup> groups;
         std::vector<ApplyGenString> strs;
@@ -535,30 +408,27 @@ extern "C" int ctg_exec_result_pauli_apply(ctg_exec* e, int64_t rank, const int6
         const int64_t g_bytes = (int64_t)groups.size() * (int64_t)sizeof(ApplyGenGroup);
         const int64_t s_bytes = (int64_t)strs.size() * (int64_t)sizeof(ApplyGenString);
         const int64_t x_bytes = (int64_t)xs.size() * 8, z_bytes = (int64_t)zs.size() * 8;
-        {
-            const int rc = reduce_reserve(e, up256(g_bytes) + up256(s_bytes) + up256(x_bytes) + up256(z_bytes) + stage_bytes);
-            if (rc != CTG_OK) return rc;
-        }
-        ApplyGenGroup* d_groups = (ApplyGenGroup*)e->d_reduce;
-        ApplyGenString* d_strs = (ApplyGenString*)((char*)d_groups + up256(g_bytes));
-        int64_t* d_xs = (int64_t*)((char*)d_strs + up256(s_bytes));
-        int64_t* d_zs = (int64_t*)((char*)d_xs + up256(x_bytes));
-        if (!y) y = (char*)d_zs + up256(z_bytes);
-        HIP_TRY_A(upload(d_groups, groups.data(), g_bytes, st));
-        HIP_TRY_A(upload(d_strs, strs.data(), s_bytes, st));
-        if (x_bytes) HIP_TRY_A(upload(d_xs, xs.data(), x_bytes, st));
-        if (z_bytes) HIP_TRY_A(upload(d_zs, zs.data(), z_bytes, st));
-        int rc;
-        const int ng = (int)groups.size();
-        switch (dtype) {
-            case CTG_F32: rc = apply_general_launch<float>(e, n, d_groups, ng, d_strs, d_xs, d_zs, y); break;
-            case CTG_F64: rc = apply_general_launch<double>(e, n, d_groups, ng, d_strs, d_xs, d_zs, y); break;
-            case CTG_C64: rc = apply_general_launch<float2>(e, n, d_groups, ng, d_strs, d_xs, d_zs, y); break;
-            default: rc = apply_general_launch<double2>(e, n, d_groups, ng, d_strs, d_xs, d_zs, y); break;
-        }
+        ApplyGenGroup* d_groups = nullptr;
+        ApplyGenString* d_strs = nullptr;
+        int64_t *d_xs = nullptr, *d_zs = nullptr;
+        auto lay = [&](void* base) {
+            Carve c(base);
+            d_groups = c.take<ApplyGenGroup>(g_bytes);
+            d_strs = c.take<ApplyGenString>(s_bytes);
+            d_xs = c.take<int64_t>(x_bytes);
+            d_zs = c.take<int64_t>(z_bytes);
+            y = out.y(c.take<char>(out.stage_bytes()));
+            return c.bytes();
+        };
+        rc = reduce_reserve(e, lay(nullptr));
         if (rc != CTG_OK) return rc;
-        if (host_out) HIP_TRY_A(hipMemcpyAsync(host_out, y, (size_t)bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY_A(hipStreamSynchronize(st));
+        lay(e->d_reduce);
+        HIP_TRY(upload(d_groups, groups.data(), g_bytes, st));
+        HIP_TRY(upload(d_strs, strs.data(), s_bytes, st));
+        if (x_bytes) HIP_TRY(upload(d_xs, xs.data(), x_bytes, st));
+        if (z_bytes) HIP_TRY(upload(d_zs, zs.data(), z_bytes, st));
+        const int ng = (int)groups.size();
+        rc = dispatch_elem(dtype, [&](auto t) { return apply_general_launch<decltype(t)>(e, n, d_groups, ng, d_strs, d_xs, d_zs, y); });
     }
-    return CTG_OK;
+    return out.finish(rc, y, st);
 }

@@ -7,10 +7,10 @@
 // product is formed in fp64 (exact for float / complex64 elements), every sum is in fp64 with an association that is a
 // function of (extents, keep) alone; no atomics.  The axes are split as for a marginal (marginal_plan).  Two routes:
 //
-//   power of two (every extent a power of two, at least kRdmChunk = 4096 elements): a is the bit-extract of the flat
+//   power of two (every extent a power of two, at least kResultChunk = 4096 elements): a is the bit-extract of the flat
 //   index under the keep mask K, r the one under its complement.  For D < 16 the lowest 4 - log2(D) bits of r are
 //   folded into the row: D' = 16 rows (a, s), and rho[a, b] is the sum over s of G'[(a, s), (b, s)].  A chunk is the
-//   next 12 - log2(D') bits of r for all D' rows: kRdmChunk elements that lie in runs of at least 64 consecutive ones
+//   next 12 - log2(D') bits of r for all D' rows: kResultChunk elements that lie in runs of at least 64 consecutive ones
 //   (every bit of the flat index below the chunk's highest complement bit is a row bit or a chunk bit).
 //
 //     rdm_chunk_kernel<T, NT>  NT = D' / 16 in {1, 2, 4}.  A workgroup takes the chunks wg, wg + grid, ... in
@@ -27,7 +27,7 @@
 //     rdm_finish_kernel        adds those in ascending order, then the folded s ascending; writes b <= a, the
 //                              conjugate half and the zero imaginary diagonal.
 //
-//   grid = min(kRdmMaxGrid, ceil(chunks / kRdmMinChunks)): two workgroups per CU at most (LDS: 66 KiB each for complex
+//   grid = result_chunk_grid(chunks) = min(512, ceil(chunks / 3)): two workgroups per CU at most (LDS: 66 KiB each for complex
 //   elements), and at least three chunks per workgroup (all but the last ones), so that a workgroup's partial -- up
 //   to 40 KiB -- is at most a third of what it read.
 //
@@ -35,23 +35,16 @@
 //   walks its chunk serially with the mixed-radix decode of marg_general_kernel; rdm_general_finish_kernel adds the
 //   chunks in ascending order.  Not tuned.
 #include <algorithm>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
 
-#include "ctg_exec_state.h"
-#include "ctg_sample_elem.h"
+#include "ctg_result_elem.h"
+#include "ctg_result_host.h"
 
 namespace ctg {
 
-constexpr int kRdmChunk = kSampleBlock;          // elements of a chunk: D' rows x TC columns
-constexpr int kRdmBits = 12;                     // log2(kRdmChunk)
-constexpr int kRdmMaxGrid = 512;                 // workgroups of rdm_chunk_kernel
-constexpr int kRdmMinChunks = 3;                 // chunks per workgroup before the grid grows
+// (a chunk, kResultChunk elements of ctg_result_elem.h, is D' rows x TC columns here)
 constexpr int kRdmSumChunk = 32;                 // partials per work item of rdm_gather_kernel
 constexpr int64_t kRdmGeneralChunk = 1024;       // complement positions per work item of the general route, at least
 constexpr int64_t kRdmGeneralMaxChunks = 1024;   // ... and at most this many chunks per pair
-static_assert(kRdmChunk == 1 << kRdmBits, "a chunk is addressed by kRdmBits bits");
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
@@ -82,30 +75,20 @@ template <> struct RdmElem<double2> {
 // element's place in an LDS plane (row * LD or column).  The bits are those of the flat index under the chunk's mask,
 // lowest first, so e and the flat index agree in their lowest bits: consecutive e are consecutive elements.
 struct RdmChunkBits {
-    int64_t gpos[kRdmBits];
-    int32_t lw[kRdmBits];
+    int64_t gpos[kResultChunkBits];
+    int32_t lw[kResultChunkBits];
 };
 
 __device__ __forceinline__ int64_t rdm_goff(uint32_t e, const RdmChunkBits& b) {
     int64_t r = 0;
 #pragma unroll
-    for (int i = 0; i < kRdmBits; ++i) r += ((e >> i) & 1u) ? b.gpos[i] : 0;
+    for (int i = 0; i < kResultChunkBits; ++i) r += ((e >> i) & 1u) ? b.gpos[i] : 0;
     return r;
 }
 __device__ __forceinline__ int rdm_loff(uint32_t e, const RdmChunkBits& b) {
     int r = 0;
 #pragma unroll
-    for (int i = 0; i < kRdmBits; ++i) r += ((e >> i) & 1u) ? b.lw[i] : 0;
-    return r;
-}
-
-// the bits of v dealt to the set bits of mask, lowest first
-__host__ __device__ __forceinline__ int64_t rdm_deposit(int64_t v, int64_t mask) {
-    int64_t r = 0;
-    for (int64_t m = mask; m && v; m &= m - 1) {
-        if (v & 1) r |= m & (0 - m);
-        v >>= 1;
-    }
+    for (int i = 0; i < kResultChunkBits; ++i) r += ((e >> i) & 1u) ? b.lw[i] : 0;
     return r;
 }
 
@@ -115,8 +98,8 @@ __global__ __launch_bounds__(kSampleThreads, 2) void rdm_chunk_kernel(const T* _
                                                                       double* __restrict__ part) {
     constexpr int P = RdmElem<T>::P;
     constexpr int V = 16 / sizeof(T);
-    constexpr int G = kRdmChunk / V / kSampleThreads;
-    constexpr int DP = 16 * NT, TC = kRdmChunk / DP, LD = TC + 2, PLANE = DP * LD;
+    constexpr int G = kResultChunk / V / kSampleThreads;
+    constexpr int DP = 16 * NT, TC = kResultChunk / DP, LD = TC + 2, PLANE = DP * LD;
     constexpr int NTL = NT * (NT + 1) / 2;
     constexpr int WC = TC / (kSampleThreads / 64);   // columns of a wave
     static_assert(WC % 8 == 0, "a wave multiplies eight columns per step");
@@ -139,7 +122,7 @@ __global__ __launch_bounds__(kSampleThreads, 2) void rdm_chunk_kernel(const T* _
 
     T st[G][V];
     auto fetch = [&](int64_t q) {
-        const int64_t base = rdm_deposit(q, rhi);
+        const int64_t base = deposit_bits(q, rhi);
 #pragma unroll
         for (int g = 0; g < G; ++g)
             load_group<T>(x, base + goff_t + rdm_goff((uint32_t)(g * kSampleThreads) * V, bits), n, vec != 0, st[g]);
@@ -343,32 +326,6 @@ using namespace ctg;
 
 namespace {
 
-int rfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    ctg_set_error_(buf);
-    return code;
-}
-
-#define HIP_TRY_R(expr)                                                                                    \
-    do {                                                                                                   \
-        hipError_t _e = (expr);                                                                            \
-        if (_e != hipSuccess)                                                                              \
-            return rfail(_e == hipErrorOutOfMemory ? CTG_E_NOMEM : CTG_E_HIP, "%s failed: %s", #expr,      \
-                         hipGetErrorString(_e));                                                           \
-    } while (0)
-
-#define LAUNCH_CHECK(name)                                                                                 \
-    do {                                                                                                   \
-        hipError_t _e = hipGetLastError();                                                                 \
-        if (_e != hipSuccess) return rfail(CTG_E_HIP, name " launch failed: %s", hipGetErrorString(_e));   \
-    } while (0)
-
-int64_t up256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
 int popcount64(int64_t v) { return __builtin_popcountll((unsigned long long)v); }
 
 // the lowest `k` set bits of mask
@@ -378,15 +335,6 @@ int64_t lowest_bits(int64_t mask, int k) {
         r |= mask & (0 - mask);
         mask &= mask - 1;
     }
-    return r;
-}
-
-// the bits of v under the set bits of mask, squeezed together
-int64_t extract_bits(int64_t v, int64_t mask) {
-    int64_t r = 0;
-    int o = 0;
-    for (int b = 0; b < 63; ++b)
-        if ((mask >> b) & 1) r |= ((v >> b) & 1) << o++;
     return r;
 }
 
@@ -409,10 +357,10 @@ RdmFastPlan rdm_fast_plan(int64_t n, int64_t keepmask, int D, int P) {
     const int64_t F = lowest_bits(R, f), K2 = keepmask | F;
     const int d2 = d + f;
     fp.nt = 1 << (d2 - 4);
-    const int64_t Rlo = lowest_bits(R & ~F, kRdmBits - d2);
+    const int64_t Rlo = lowest_bits(R & ~F, kResultChunkBits - d2);
     const int64_t M = K2 | Rlo;
     fp.rhi = R & ~F & ~Rlo;
-    const int ld = kRdmChunk / (16 * fp.nt) + 2;
+    const int ld = kResultChunk / (16 * fp.nt) + 2;
     int i = 0;
     for (int b = 0; b < 63; ++b) {
         if (!((M >> b) & 1)) continue;
@@ -425,9 +373,9 @@ RdmFastPlan rdm_fast_plan(int64_t n, int64_t keepmask, int D, int P) {
     fp.fold.S = 1 << f;
     for (int a = 0; a < D; ++a)
         for (int s = 0; s < fp.fold.S; ++s)
-            fp.fold.row[a * fp.fold.S + s] = (uint8_t)extract_bits(rdm_deposit(a, keepmask) | rdm_deposit(s, F), K2);
-    fp.nchunks = n / kRdmChunk;
-    fp.grid = (int)std::min<int64_t>(kRdmMaxGrid, (fp.nchunks + kRdmMinChunks - 1) / kRdmMinChunks);
+            fp.fold.row[a * fp.fold.S + s] = (uint8_t)extract_bits(deposit_bits(a, keepmask) | deposit_bits(s, F), K2);
+    fp.nchunks = n / kResultChunk;
+    fp.grid = result_chunk_grid(fp.nchunks);
     fp.ngroups = (fp.grid + kRdmSumChunk - 1) / kRdmSumChunk;
     fp.E = (int64_t)(fp.nt * (fp.nt + 1) / 2) * P * 256;
     return fp;
@@ -482,22 +430,16 @@ int rdm_general(ctg_exec* e, const MargAxes& ax, int D, int64_t rc, double* B, d
 }  // namespace
 
 extern "C" int ctg_exec_result_rdm(ctg_exec* e, int64_t rank, const int64_t* extents, const int32_t* keep, void* out) {
-    if (!e || !out) return rfail(CTG_E_INVALID, "null argument");
+    if (!e || !out) return result_fail(CTG_E_INVALID, "null argument");
     MarginalPlan mp;
     const char* why = "";
     if (marginal_plan(rank, extents, keep, e->plan->result_elems, &mp, &why) != CTG_OK)
-        return rfail(CTG_E_INVALID, "rdm: %s", why);
+        return result_fail(CTG_E_INVALID, "rdm: %s", why);
     if (mp.m > CTG_RDM_MAX_DIM)
-        return rfail(CTG_E_INVALID, "rdm: the kept extents' product is %lld; at most CTG_RDM_MAX_DIM = %d", (long long)mp.m,
+        return result_fail(CTG_E_INVALID, "rdm: the kept extents' product is %lld; at most CTG_RDM_MAX_DIM = %d", (long long)mp.m,
                      CTG_RDM_MAX_DIM);
-    {
-        // sum p of the result by the statistics passes of ctg_sample.hip (synchronises)
-        double sum_p = 0.0;
-        const int rc = ctg_exec_result_stats(e, &sum_p, nullptr, nullptr, nullptr);
-        if (rc != CTG_OK) return rc;
-        if (!std::isfinite(sum_p))
-            return rfail(CTG_E_NORM, "the result tensor's sum of |x|^2 is %g: no reduced density matrix of it", sum_p);
-    }
+    int rc = result_norm_finite(e, "no reduced density matrix of it");
+    if (rc != CTG_OK) return rc;
     const int dtype = e->plan->dtype;
     const int P = (dtype == CTG_C64 || dtype == CTG_C128) ? 2 : 1;
     const int D = (int)mp.m;
@@ -513,31 +455,23 @@ extern "C" int ctg_exec_result_rdm(ctg_exec* e, int64_t rank, const int64_t* ext
         const int64_t chunk = rdm_general_chunk(mp.rc);
         b_elems = (int64_t)D * D * P * ((mp.rc + chunk - 1) / chunk);
     }
-    {
-        const int rc = reduce_reserve(e, up256(out_bytes) + up256(a_elems * 8) + up256(b_elems * 8));
-        if (rc != CTG_OK) return rc;
-    }
-    double* d_out = (double*)e->d_reduce;
-    double* A = (double*)((char*)e->d_reduce + up256(out_bytes));
-    double* B = (double*)((char*)A + up256(a_elems * 8));
-    int rc;
-    if (mp.fast) {
-        switch (dtype) {
-            case CTG_F32: rc = rdm_fast<float>(e, fp, mp.n, A, B, d_out); break;
-            case CTG_F64: rc = rdm_fast<double>(e, fp, mp.n, A, B, d_out); break;
-            case CTG_C64: rc = rdm_fast<float2>(e, fp, mp.n, A, B, d_out); break;
-            default: rc = rdm_fast<double2>(e, fp, mp.n, A, B, d_out); break;
-        }
-    } else {
-        switch (dtype) {
-            case CTG_F32: rc = rdm_general<float>(e, mp.ax, D, mp.rc, B, d_out); break;
-            case CTG_F64: rc = rdm_general<double>(e, mp.ax, D, mp.rc, B, d_out); break;
-            case CTG_C64: rc = rdm_general<float2>(e, mp.ax, D, mp.rc, B, d_out); break;
-            default: rc = rdm_general<double2>(e, mp.ax, D, mp.rc, B, d_out); break;
-        }
-    }
+    double *d_out = nullptr, *A = nullptr, *B = nullptr;
+    auto lay = [&](void* base) {
+        Carve c(base);
+        d_out = c.take<double>(out_bytes);
+        A = c.take<double>(a_elems * 8);
+        B = c.take<double>(b_elems * 8);
+        return c.bytes();
+    };
+    rc = reduce_reserve(e, lay(nullptr));
     if (rc != CTG_OK) return rc;
-    HIP_TRY_R(hipMemcpyAsync(out, d_out, (size_t)out_bytes, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY_R(hipStreamSynchronize(e->stream));
+    lay(e->d_reduce);
+    if (mp.fast)
+        rc = dispatch_elem(dtype, [&](auto t) { return rdm_fast<decltype(t)>(e, fp, mp.n, A, B, d_out); });
+    else
+        rc = dispatch_elem(dtype, [&](auto t) { return rdm_general<decltype(t)>(e, mp.ax, D, mp.rc, B, d_out); });
+    if (rc != CTG_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)out_bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return CTG_OK;
 }

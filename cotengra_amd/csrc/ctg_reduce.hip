@@ -41,14 +41,9 @@
 //
 // Every sum has a fixed association that depends on (extents, keep) alone, and there are no atomics in either route.
 #include <algorithm>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 #include <numeric>
-#include <vector>
 
-#include "ctg_exec_state.h"
+#include "ctg_result_host.h"
 #include "ctg_sample_elem.h"
 
 namespace ctg {
@@ -515,44 +510,6 @@ using namespace ctg;
 
 namespace {
 
-int rfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    ctg_set_error_(buf);
-    return code;
-}
-
-#define HIP_TRY_R(expr)                                                                                    \
-    do {                                                                                                   \
-        hipError_t _e = (expr);                                                                            \
-        if (_e != hipSuccess)                                                                              \
-            return rfail(_e == hipErrorOutOfMemory ? CTG_E_NOMEM : CTG_E_HIP, "%s failed: %s", #expr,      \
-                         hipGetErrorString(_e));                                                           \
-    } while (0)
-
-#define LAUNCH_CHECK(name)                                                                                 \
-    do {                                                                                                   \
-        hipError_t _e = hipGetLastError();                                                                 \
-        if (_e != hipSuccess) return rfail(CTG_E_HIP, name " launch failed: %s", hipGetErrorString(_e));   \
-    } while (0)
-
-int64_t up256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
-int reserve(ctg_exec* e, int64_t want) { return reduce_reserve(e, want); }
-
-// sum p of the result by the statistics passes of ctg_sample.hip (synchronises): CTG_E_NORM unless finite
-int check_norm(ctg_exec* e, const char* what) {
-    double sum_p = 0.0;
-    const int rc = ctg_exec_result_stats(e, &sum_p, nullptr, nullptr, nullptr);
-    if (rc != CTG_OK) return rc;
-    if (!std::isfinite(sum_p))
-        return rfail(CTG_E_NORM, "the result tensor's sum of |x|^2 is %g: no %s of it", sum_p, what);
-    return CTG_OK;
-}
-
 struct TopkBufs {
     TopkState* st;
     uint32_t* rows;
@@ -566,26 +523,21 @@ struct TopkBufs {
     int64_t bytes;
 };
 
-TopkBufs topk_carve(char* base, int64_t nb, int64_t grid, int64_t k) {
+TopkBufs topk_carve(void* base, int64_t nb, int64_t grid, int64_t k) {
     TopkBufs b;
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) {
-        char* p = base ? base + o : nullptr;
-        o += up256(bytes);
-        return p;
-    };
-    b.st = (TopkState*)take(sizeof(TopkState));
-    b.rows = (uint32_t*)take(grid * kBins * 4);
-    b.tot = (unsigned long long*)take(kBins * 8);
-    b.cg = (uint32_t*)take(nb * 4);
-    b.ce = (uint32_t*)take(nb * 4);
-    b.og = (int64_t*)take(nb * 8);
-    b.oe = (int64_t*)take(nb * 8);
-    b.keys = (unsigned long long*)take(kTopkCompact * 8);
-    b.el = take(k * 16);
-    b.idx = (int64_t*)take(k * 8);
-    b.p = (double*)take(k * 8);
-    b.bytes = o;
+    Carve c(base);
+    b.st = c.take<TopkState>(sizeof(TopkState));
+    b.rows = c.take<uint32_t>(grid * kBins * 4);
+    b.tot = c.take<unsigned long long>(kBins * 8);
+    b.cg = c.take<uint32_t>(nb * 4);
+    b.ce = c.take<uint32_t>(nb * 4);
+    b.og = c.take<int64_t>(nb * 8);
+    b.oe = c.take<int64_t>(nb * 8);
+    b.keys = c.take<unsigned long long>(kTopkCompact * 8);
+    b.el = c.take<char>(k * 16);
+    b.idx = c.take<int64_t>(k * 8);
+    b.p = c.take<double>(k * 8);
+    b.bytes = c.bytes();
     return b;
 }
 
@@ -595,7 +547,7 @@ int topk_run(ctg_exec* e, const TopkBufs& b, int64_t n, int64_t nb, int grid, in
     const int vec = ((uintptr_t)e->d_result & 15) == 0 ? 1 : 0;
     hipStream_t s = e->stream;
     TopkState h{0ull, (long long)k, (long long)n, 0ll};
-    HIP_TRY_R(hipMemcpyAsync(b.st, &h, sizeof(h), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(b.st, &h, sizeof(h), hipMemcpyHostToDevice, s));
     const int64_t gs = std::max<int64_t>((nb + kSelThreads - 1) / kSelThreads, 1);
     int sh = 64;
     while (sh > 0) {
@@ -621,8 +573,8 @@ int topk_run(ctg_exec* e, const TopkBufs& b, int64_t n, int64_t nb, int grid, in
         topk_select_kernel<<<dim3(1), dim3(kSelThreads), 0, s>>>(b.tot, b.st, bits);
         LAUNCH_CHECK("topk_select_kernel");
         sh -= bits;
-        HIP_TRY_R(hipMemcpyAsync(&h, b.st, sizeof(h), hipMemcpyDeviceToHost, s));
-        HIP_TRY_R(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpyAsync(&h, b.st, sizeof(h), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
     }
     // every key above the threshold, and the first krem equal to it by index
     topk_count_kernel<T><<<dim3((unsigned)nb), dim3(kSampleThreads), 0, s>>>(x, n, vec, b.st, 0, b.cg, b.ce);
@@ -639,15 +591,6 @@ int floor_log2(int64_t v) {
     int l = 0;
     while ((v >> l) > 1) ++l;
     return l;
-}
-
-// the bits of v under the set bits of mask, squeezed together
-int64_t extract_bits(int64_t v, int64_t mask) {
-    int64_t r = 0;
-    int o = 0;
-    for (int b = 0; b < 63; ++b)
-        if ((mask >> b) & 1) r |= ((v >> b) & 1) << o++;
-    return r;
 }
 
 // fast route: out (device, m doubles) <- the marginal under the keep bitmask `mask` of the n = 2^L >= 4096 elements
@@ -699,18 +642,18 @@ int marginal_general(ctg_exec* e, const MargAxes& ax, int64_t m, int64_t rc, dou
 
 }  // namespace
 
-// marginal_plan and reduce_reserve of ctg_exec_state.h (ctg_rdm.hip shares them)
+// marginal_plan (ctg_rdm.hip shares it) and reduce_reserve (every later result-tensor source does) of ctg_exec_state.h
 namespace ctg {
 
 // the executor's scratch of this file, at least `want` bytes (the stream is idle: the statistics call synchronised it)
 int reduce_reserve(ctg_exec* e, int64_t want) {
     if (e->reduce_bytes >= want) return CTG_OK;
     if (e->d_reduce) {
-        HIP_TRY_R(hipFree(e->d_reduce));
+        HIP_TRY(hipFree(e->d_reduce));
         e->d_reduce = nullptr;
         e->reduce_bytes = 0;
     }
-    HIP_TRY_R(hipMalloc(&e->d_reduce, (size_t)want));
+    HIP_TRY(hipMalloc(&e->d_reduce, (size_t)want));
     e->reduce_bytes = want;
     return CTG_OK;
 }
@@ -719,15 +662,20 @@ int reduce_reserve(ctg_exec* e, int64_t want) {
 int marginal_plan(int64_t rank, const int64_t* extents, const int32_t* keep, int64_t result_elems, MarginalPlan* out,
                   const char** why) {
     MarginalPlan p;
-    if (rank < 0) return *why = "negative rank", CTG_E_INVALID;
     if (rank > 0 && (!extents || !keep)) return *why = "null argument", CTG_E_INVALID;
+    // the shape; a keep entry in front of the place where the shape is refused is named first: the axes are checked
+    // one by one, the extent, the keep entry and the running product of each
+    ResultShape shape;
+    const char* bad = nullptr;
+    const bool whole = rank == 0 && result_elems > 1;
+    if (!whole) result_shape(rank, extents, result_elems, &shape, &bad);
+    for (int64_t a = 0; a < rank && (a < shape.stop || (a == shape.stop && extents[a] >= 1)); ++a)
+        if (keep[a] != 0 && keep[a] != 1) return *why = "a keep entry is neither 0 nor 1", CTG_E_INVALID;
+    if (bad) return *why = bad, CTG_E_INVALID;
+    p.n = shape.n;
     std::vector<int64_t> ext;
     std::vector<int> kp;
     for (int64_t a = 0; a < rank; ++a) {
-        if (extents[a] < 1) return *why = "an extent is not positive", CTG_E_INVALID;
-        if (keep[a] != 0 && keep[a] != 1) return *why = "a keep entry is neither 0 nor 1", CTG_E_INVALID;
-        if (extents[a] > kReduceMaxElems / p.n) return *why = "the extents' product does not equal result_elems", CTG_E_INVALID;
-        p.n *= extents[a];
         if (keep[a]) p.m *= extents[a];
         if (extents[a] == 1) continue;
         if (!kp.empty() && kp.back() == keep[a]) {
@@ -737,13 +685,12 @@ int marginal_plan(int64_t rank, const int64_t* extents, const int32_t* keep, int
             kp.push_back(keep[a]);
         }
     }
-    if (rank == 0 && result_elems > 1) {
+    if (whole) {
         // (no shape given: the whole tensor as one dropped axis)
         p.n = result_elems;
         ext.push_back(result_elems);
         kp.push_back(0);
     }
-    if (p.n != result_elems) return *why = "the extents' product does not equal result_elems", CTG_E_INVALID;
     p.rc = p.n / p.m;
     bool pow2 = true;
     for (int64_t v : ext) pow2 = pow2 && (v & (v - 1)) == 0;
@@ -775,39 +722,29 @@ int marginal_plan(int64_t rank, const int64_t* extents, const int32_t* keep, int
 extern "C" {
 
 int ctg_exec_result_topk(ctg_exec* e, int64_t k, int64_t* idx, void* elems, double* p) {
-    if (!e || !idx) return rfail(CTG_E_INVALID, "null argument");
+    if (!e || !idx) return result_fail(CTG_E_INVALID, "null argument");
     const int64_t n = e->plan->result_elems;
     if (k < 1 || k > n || k > CTG_TOPK_MAX)
-        return rfail(CTG_E_INVALID, "k = %lld: need 1 <= k <= min(result_elems = %lld, CTG_TOPK_MAX = %d)", (long long)k,
+        return result_fail(CTG_E_INVALID, "k = %lld: need 1 <= k <= min(result_elems = %lld, CTG_TOPK_MAX = %d)", (long long)k,
                      (long long)n, CTG_TOPK_MAX);
-    if (n > kReduceMaxElems) return rfail(CTG_E_INVALID, "result tensor too large (%lld elements)", (long long)n);
-    {
-        const int rc = check_norm(e, "top-k");
-        if (rc != CTG_OK) return rc;
-    }
+    if (n > kReduceMaxElems) return result_fail(CTG_E_INVALID, "result tensor too large (%lld elements)", (long long)n);
+    int rc = result_norm_finite(e, "no top-k of it");
+    if (rc != CTG_OK) return rc;
     const int64_t nb = (n + kSampleBlock - 1) / kSampleBlock;
     const int grid = (int)std::min<int64_t>(nb, kHistMaxGrid);
-    {
-        const int rc = reserve(e, topk_carve(nullptr, nb, grid, k).bytes);
-        if (rc != CTG_OK) return rc;
-    }
-    const TopkBufs b = topk_carve((char*)e->d_reduce, nb, grid, k);
-    int rc;
-    switch (e->plan->dtype) {
-        case CTG_F32: rc = topk_run<float>(e, b, n, nb, grid, k); break;
-        case CTG_F64: rc = topk_run<double>(e, b, n, nb, grid, k); break;
-        case CTG_C64: rc = topk_run<float2>(e, b, n, nb, grid, k); break;
-        default: rc = topk_run<double2>(e, b, n, nb, grid, k); break;
-    }
+    rc = reduce_reserve(e, topk_carve(nullptr, nb, grid, k).bytes);
+    if (rc != CTG_OK) return rc;
+    const TopkBufs b = topk_carve(e->d_reduce, nb, grid, k);
+    rc = dispatch_elem(e->plan->dtype, [&](auto t) { return topk_run<decltype(t)>(e, b, n, nb, grid, k); });
     if (rc != CTG_OK) return rc;
     const int64_t isz = ctg_item_size(e->plan->dtype);
     std::vector<int64_t> hi((size_t)k);
     std::vector<double> hp((size_t)k);
     std::vector<char> he((size_t)(k * isz));
-    HIP_TRY_R(hipMemcpyAsync(hi.data(), b.idx, k * 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY_R(hipMemcpyAsync(hp.data(), b.p, k * 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY_R(hipMemcpyAsync(he.data(), b.el, k * isz, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY_R(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpyAsync(hi.data(), b.idx, k * 8, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(hp.data(), b.p, k * 8, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(he.data(), b.el, k * isz, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     // the order of the k records: p descending, the lower index first among equals (host; only k records came over)
     std::vector<int64_t> ord((size_t)k);
     std::iota(ord.begin(), ord.end(), (int64_t)0);
@@ -822,15 +759,13 @@ int ctg_exec_result_topk(ctg_exec* e, int64_t k, int64_t* idx, void* elems, doub
 }
 
 int ctg_exec_result_marginal(ctg_exec* e, int64_t rank, const int64_t* extents, const int32_t* keep, double* out) {
-    if (!e || !out) return rfail(CTG_E_INVALID, "null argument");
+    if (!e || !out) return result_fail(CTG_E_INVALID, "null argument");
     MarginalPlan mp;
     const char* why = "";
     if (marginal_plan(rank, extents, keep, e->plan->result_elems, &mp, &why) != CTG_OK)
-        return rfail(CTG_E_INVALID, "marginal: %s", why);
-    {
-        const int rc = check_norm(e, "marginal");
-        if (rc != CTG_OK) return rc;
-    }
+        return result_fail(CTG_E_INVALID, "marginal: %s", why);
+    int rc = result_norm_finite(e, "no marginal of it");
+    if (rc != CTG_OK) return rc;
     // [out: m | A: partials of a slab | B: per-chunk sums]
     int64_t a_elems = 0, b_elems = 0;
     if (mp.fast) {
@@ -839,32 +774,24 @@ int ctg_exec_result_marginal(ctg_exec* e, int64_t rank, const int64_t* extents, 
     } else {
         b_elems = mp.m * ((mp.rc + kMargGeneralChunk - 1) / kMargGeneralChunk);
     }
-    {
-        const int rc = reserve(e, up256(mp.m * 8) + up256(a_elems * 8) + up256(b_elems * 8));
-        if (rc != CTG_OK) return rc;
-    }
-    double* d_out = (double*)e->d_reduce;
-    double* A = (double*)((char*)e->d_reduce + up256(mp.m * 8));
-    double* B = (double*)((char*)A + up256(a_elems * 8));
-    int rc;
-    if (mp.fast) {
-        switch (e->plan->dtype) {
-            case CTG_F32: rc = marginal_fast<float>(e, mp.n, mp.mask, A, B, d_out); break;
-            case CTG_F64: rc = marginal_fast<double>(e, mp.n, mp.mask, A, B, d_out); break;
-            case CTG_C64: rc = marginal_fast<float2>(e, mp.n, mp.mask, A, B, d_out); break;
-            default: rc = marginal_fast<double2>(e, mp.n, mp.mask, A, B, d_out); break;
-        }
-    } else {
-        switch (e->plan->dtype) {
-            case CTG_F32: rc = marginal_general<float>(e, mp.ax, mp.m, mp.rc, B, d_out); break;
-            case CTG_F64: rc = marginal_general<double>(e, mp.ax, mp.m, mp.rc, B, d_out); break;
-            case CTG_C64: rc = marginal_general<float2>(e, mp.ax, mp.m, mp.rc, B, d_out); break;
-            default: rc = marginal_general<double2>(e, mp.ax, mp.m, mp.rc, B, d_out); break;
-        }
-    }
+    double *d_out = nullptr, *A = nullptr, *B = nullptr;
+    auto lay = [&](void* base) {
+        Carve c(base);
+        d_out = c.take<double>(mp.m * 8);
+        A = c.take<double>(a_elems * 8);
+        B = c.take<double>(b_elems * 8);
+        return c.bytes();
+    };
+    rc = reduce_reserve(e, lay(nullptr));
     if (rc != CTG_OK) return rc;
-    HIP_TRY_R(hipMemcpyAsync(out, d_out, mp.m * 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY_R(hipStreamSynchronize(e->stream));
+    lay(e->d_reduce);
+    if (mp.fast)
+        rc = dispatch_elem(e->plan->dtype, [&](auto t) { return marginal_fast<decltype(t)>(e, mp.n, mp.mask, A, B, d_out); });
+    else
+        rc = dispatch_elem(e->plan->dtype, [&](auto t) { return marginal_general<decltype(t)>(e, mp.ax, mp.m, mp.rc, B, d_out); });
+    if (rc != CTG_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, d_out, mp.m * 8, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return CTG_OK;
 }
 

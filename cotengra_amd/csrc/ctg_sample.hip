@@ -21,12 +21,7 @@
 // C_b may exceed every running sum of the block.  The draw is then the block's last element with p > 0; and both
 // predicates ask for p > 0 (L > 0 of a lane), so that no rounding of the scan can return an element of
 // probability zero.
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-
-#include "ctg_exec_state.h"
+#include "ctg_result_host.h"
 #include "ctg_sample_elem.h"
 
 namespace ctg {
@@ -254,24 +249,6 @@ using namespace ctg;
 
 namespace {
 
-int sfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    ctg_set_error_(buf);
-    return code;
-}
-
-#define HIP_TRY_S(expr)                                                                                    \
-    do {                                                                                                   \
-        hipError_t _e = (expr);                                                                            \
-        if (_e != hipSuccess)                                                                              \
-            return sfail(_e == hipErrorOutOfMemory ? CTG_E_NOMEM : CTG_E_HIP, "%s failed: %s", #expr,      \
-                         hipGetErrorString(_e));                                                           \
-    } while (0)
-
 // per-block arrays [S | Q | M | I | C] of nb words each, then 4 words of statistics
 int64_t blocks_bytes(int64_t nb) { return (5 * nb + 4) * 8; }
 // per draw: the element (16 bytes reserved, first: aligned for every dtype), u, idx, p (8 bytes each)
@@ -280,11 +257,11 @@ int64_t io_bytes(int64_t ns) { return ns * 40; }
 int grow(void** buf, int64_t* have, int64_t want) {
     if (*have >= want) return CTG_OK;
     if (*buf) {
-        HIP_TRY_S(hipFree(*buf));
+        HIP_TRY(hipFree(*buf));
         *buf = nullptr;
         *have = 0;
     }
-    HIP_TRY_S(hipMalloc(buf, (size_t)want));
+    HIP_TRY(hipMalloc(buf, (size_t)want));
     *have = want;
     return CTG_OK;
 }
@@ -308,19 +285,17 @@ Blocks carve(const ctg_exec* e) {
 }
 
 template <typename T>
-hipError_t launch_block_pass(const ctg_exec* e, const Blocks& b, int vec) {
+void launch_block_pass(const ctg_exec* e, const Blocks& b, int vec) {
     prob_block_kernel<T><<<dim3((unsigned)b.nb), dim3(kSampleThreads), 0, e->stream>>>(
         (const T*)e->d_result, e->plan->result_elems, vec, b.S, b.Q, b.M, b.I);
-    return hipGetLastError();
 }
 
 template <typename T>
-hipError_t launch_sample(const ctg_exec* e, const Blocks& b, int vec, const double* d_u, int64_t ns, int64_t* d_idx,
+void launch_sample(const ctg_exec* e, const Blocks& b, int vec, const double* d_u, int64_t ns, int64_t* d_idx,
                          void* d_el, double* d_p) {
     const int per = kSampleThreads / 64;
     sample_kernel<T><<<dim3((unsigned)((ns + per - 1) / per)), dim3(kSampleThreads), 0, e->stream>>>(
         (const T*)e->d_result, e->plan->result_elems, vec, b.C, b.nb, d_u, ns, d_idx, (T*)d_el, d_p);
-    return hipGetLastError();
 }
 
 // passes 1 and 2 on the executor's stream, the four statistics on the host (synchronises)
@@ -328,37 +303,30 @@ int run_stats(ctg_exec* e, Blocks* out, int* vec_out, double host[4]) {
     const ctg_plan* p = e->plan;
     const int64_t n = p->result_elems;
     const int64_t nb = (n + kSampleBlock - 1) / kSampleBlock;
-    if (nb > 0x7fffffffll) return sfail(CTG_E_INVALID, "result tensor too large to sample (%lld elements)", (long long)n);
-    HIP_TRY_S(hipSetDevice(e->device));
+    if (nb > 0x7fffffffll) return result_fail(CTG_E_INVALID, "result tensor too large to sample (%lld elements)", (long long)n);
+    HIP_TRY(hipSetDevice(e->device));
     if (e->sample_blocks_bytes < blocks_bytes(nb)) {
-        HIP_TRY_S(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
         const int rc = grow(&e->d_sample_blocks, &e->sample_blocks_bytes, blocks_bytes(nb));
         if (rc != CTG_OK) return rc;
     }
     const Blocks b = carve(e);
     const int vec = ((uintptr_t)e->d_result & 15) == 0 ? 1 : 0;
     for (hipEvent_t& ev : e->sample_ev)
-        if (!ev) HIP_TRY_S(hipEventCreate(&ev));
+        if (!ev) HIP_TRY(hipEventCreate(&ev));
     e->sample_last_valid = false;
-    HIP_TRY_S(hipEventRecord(e->sample_ev[0], e->stream));
-    hipError_t err = hipSuccess;
-    switch (p->dtype) {
-        case CTG_F32: err = launch_block_pass<float>(e, b, vec); break;
-        case CTG_F64: err = launch_block_pass<double>(e, b, vec); break;
-        case CTG_C64: err = launch_block_pass<float2>(e, b, vec); break;
-        default: err = launch_block_pass<double2>(e, b, vec); break;
-    }
-    if (err != hipSuccess) return sfail(CTG_E_HIP, "prob_block_kernel launch failed: %s", hipGetErrorString(err));
-    HIP_TRY_S(hipEventRecord(e->sample_ev[1], e->stream));
+    HIP_TRY(hipEventRecord(e->sample_ev[0], e->stream));
+    dispatch_elem(p->dtype, [&](auto t) { launch_block_pass<decltype(t)>(e, b, vec); });
+    LAUNCH_CHECK("prob_block_kernel");
+    HIP_TRY(hipEventRecord(e->sample_ev[1], e->stream));
     const int64_t gs = (nb + kScanThreads - 1) / kScanThreads;
     prob_scan_kernel<<<dim3(1), dim3(kScanThreads), 0, e->stream>>>(b.S, b.Q, b.M, b.I, nb, gs < 1 ? 1 : gs, b.C, b.stats);
-    err = hipGetLastError();
-    if (err != hipSuccess) return sfail(CTG_E_HIP, "prob_scan_kernel launch failed: %s", hipGetErrorString(err));
-    HIP_TRY_S(hipEventRecord(e->sample_ev[2], e->stream));
-    HIP_TRY_S(hipMemcpyAsync(host, b.stats, 32, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY_S(hipStreamSynchronize(e->stream));
-    HIP_TRY_S(hipEventElapsedTime(&e->sample_pass_ms[0], e->sample_ev[0], e->sample_ev[1]));
-    HIP_TRY_S(hipEventElapsedTime(&e->sample_pass_ms[1], e->sample_ev[1], e->sample_ev[2]));
+    LAUNCH_CHECK("prob_scan_kernel");
+    HIP_TRY(hipEventRecord(e->sample_ev[2], e->stream));
+    HIP_TRY(hipMemcpyAsync(host, b.stats, 32, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipEventElapsedTime(&e->sample_pass_ms[0], e->sample_ev[0], e->sample_ev[1]));
+    HIP_TRY(hipEventElapsedTime(&e->sample_pass_ms[1], e->sample_ev[1], e->sample_ev[2]));
     memcpy(e->sample_last, host, 32);
     e->sample_last_valid = true;
     if (out) *out = b;
@@ -371,7 +339,7 @@ int run_stats(ctg_exec* e, Blocks* out, int* vec_out, double host[4]) {
 extern "C" {
 
 int ctg_exec_result_stats(ctg_exec* e, double* sum_p, double* sum_p2, double* max_p, int64_t* argmax) {
-    if (!e) return sfail(CTG_E_INVALID, "null argument");
+    if (!e) return result_fail(CTG_E_INVALID, "null argument");
     double host[4];
     const int rc = run_stats(e, nullptr, nullptr, host);
     if (rc != CTG_OK) return rc;
@@ -383,8 +351,8 @@ int ctg_exec_result_stats(ctg_exec* e, double* sum_p, double* sum_p2, double* ma
 }
 
 int ctg_exec_sample_info(ctg_exec* e, double* sum_p, double* sum_p2, double* max_p, int64_t* argmax, float* pass_ms) {
-    if (!e) return sfail(CTG_E_INVALID, "null argument");
-    if (!e->sample_last_valid) return sfail(CTG_E_INVALID, "no statistics or sample call has completed on this executor");
+    if (!e) return result_fail(CTG_E_INVALID, "null argument");
+    if (!e->sample_last_valid) return result_fail(CTG_E_INVALID, "no statistics or sample call has completed on this executor");
     if (sum_p) *sum_p = e->sample_last[0];
     if (sum_p2) *sum_p2 = e->sample_last[1];
     if (max_p) *max_p = e->sample_last[2];
@@ -397,13 +365,13 @@ int ctg_exec_sample_info(ctg_exec* e, double* sum_p, double* sum_p2, double* max
 }
 
 int ctg_exec_sample_result(ctg_exec* e, const double* u, int64_t n, int64_t* idx, void* elems, double* p) {
-    if (!e) return sfail(CTG_E_INVALID, "null argument");
-    if (n < 0) return sfail(CTG_E_INVALID, "negative number of draws");
+    if (!e) return result_fail(CTG_E_INVALID, "null argument");
+    if (n < 0) return result_fail(CTG_E_INVALID, "negative number of draws");
     if (n == 0) return CTG_OK;
-    if (!u || !idx) return sfail(CTG_E_INVALID, "null argument");
+    if (!u || !idx) return result_fail(CTG_E_INVALID, "null argument");
     for (int64_t s = 0; s < n; ++s)
         if (!(u[s] >= 0.0 && u[s] < 1.0))
-            return sfail(CTG_E_INVALID, "uniform %lld is %g: not in [0, 1)", (long long)s, u[s]);
+            return result_fail(CTG_E_INVALID, "uniform %lld is %g: not in [0, 1)", (long long)s, u[s]);
     Blocks b;
     int vec = 0;
     double host[4];
@@ -411,8 +379,7 @@ int ctg_exec_sample_result(ctg_exec* e, const double* u, int64_t n, int64_t* idx
         const int rc = run_stats(e, &b, &vec, host);
         if (rc != CTG_OK) return rc;
     }
-    if (!(host[0] > 0.0) || !std::isfinite(host[0]))
-        return sfail(CTG_E_NORM, "the result tensor's sum of |x|^2 is %g: nothing to draw from", host[0]);
+    if (!(host[0] > 0.0) || !std::isfinite(host[0])) return result_norm_fail(host[0], "nothing to draw from");
     const int64_t isz = ctg_item_size(e->plan->dtype);
     const int64_t chunk = n < kSampleChunk ? n : kSampleChunk;
     {
@@ -426,20 +393,14 @@ int ctg_exec_sample_result(ctg_exec* e, const double* u, int64_t n, int64_t* idx
     double* d_p = (double*)(d_idx + chunk);
     for (int64_t s0 = 0; s0 < n; s0 += chunk) {
         const int64_t ns = n - s0 < chunk ? n - s0 : chunk;
-        HIP_TRY_S(hipMemcpyAsync(d_u, u + s0, ns * 8, hipMemcpyHostToDevice, e->stream));
-        hipError_t err = hipSuccess;
-        switch (e->plan->dtype) {
-            case CTG_F32: err = launch_sample<float>(e, b, vec, d_u, ns, d_idx, d_el, d_p); break;
-            case CTG_F64: err = launch_sample<double>(e, b, vec, d_u, ns, d_idx, d_el, d_p); break;
-            case CTG_C64: err = launch_sample<float2>(e, b, vec, d_u, ns, d_idx, d_el, d_p); break;
-            default: err = launch_sample<double2>(e, b, vec, d_u, ns, d_idx, d_el, d_p); break;
-        }
-        if (err != hipSuccess) return sfail(CTG_E_HIP, "sample_kernel launch failed: %s", hipGetErrorString(err));
-        HIP_TRY_S(hipMemcpyAsync(idx + s0, d_idx, ns * 8, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(d_u, u + s0, ns * 8, hipMemcpyHostToDevice, e->stream));
+        dispatch_elem(e->plan->dtype, [&](auto t) { launch_sample<decltype(t)>(e, b, vec, d_u, ns, d_idx, d_el, d_p); });
+        LAUNCH_CHECK("sample_kernel");
+        HIP_TRY(hipMemcpyAsync(idx + s0, d_idx, ns * 8, hipMemcpyDeviceToHost, e->stream));
         if (elems)
-            HIP_TRY_S(hipMemcpyAsync((char*)elems + s0 * isz, d_el, ns * isz, hipMemcpyDeviceToHost, e->stream));
-        if (p) HIP_TRY_S(hipMemcpyAsync(p + s0, d_p, ns * 8, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY_S(hipStreamSynchronize(e->stream));
+            HIP_TRY(hipMemcpyAsync((char*)elems + s0 * isz, d_el, ns * isz, hipMemcpyDeviceToHost, e->stream));
+        if (p) HIP_TRY(hipMemcpyAsync(p + s0, d_p, ns * 8, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
     }
     return CTG_OK;
 }

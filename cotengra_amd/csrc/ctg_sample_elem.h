@@ -1,7 +1,8 @@
 // ctg_sample_elem.h -- p = |x|^2 of one element of the result tensor and the 16-byte loads that feed it: shared by
 // the kernels that reduce p over the result (ctg_sample.hip: statistics and draws; ctg_reduce.hip: top-k and
 // marginals), so that every one of them forms the same double for the same element.  ctg_rdm.hip (reduced density
-// matrices) and ctg_pauli.hip (Pauli-string expectation values) take the same loads without the square (load_group).
+// matrices), ctg_pauli.hip, ctg_pauli_apply.hip and ctg_op_apply.hip take the same loads without the square (load_group);
+// what those chunk kernels share beyond the loads is in ctg_result_elem.h.
 #pragma once
 
 #include <cstdint>

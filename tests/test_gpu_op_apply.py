@@ -307,6 +307,7 @@ def test_refusals_through_the_c_abi():
         (4, np.array([2, 2, 2, 1023], np.int64), 2, na, ax, ms, d, host, "own"),          # a wrong product
         (3, ext, 2, na, ax, ms, d, host, "own"),
         (4, np.array([2, 2, 2, 0], np.int64), 2, na, ax, ms, d, host, "own"),
+        (4, np.array([2 ** 21, 2 ** 21, 2, 2], np.int64), 2, na, ax, ms, d, host, "own"),  # past 2^40 elements before the last axis
         (4, ext, -1, na, ax, ms, d, host, "own"),                                         # m < 0
         (4, ext, many, np.ones(many, np.int32), np.zeros(many, np.int32), np.zeros(8 * many), d, host, "own"),   # too many terms
         (4, ext, 2, i32(2, 0), ax, ms, d, host, "own"),                                   # a term without axes

@@ -356,6 +356,7 @@ def test_refusals_through_the_c_abi():
         (3, np.array([2, 2, 2047], np.int64), 2, ops, out, "own"),             # a wrong product
         (2, ext, 2, ops, out, "own"),
         (3, np.array([2, 2, 0], np.int64), 2, ops, out, "own"),
+        (3, np.array([2 ** 21, 2 ** 21, 2], np.int64), 2, ops, out, "own"),    # past 2^40 elements before the last axis
         (3, ext, -1, ops, out, "own"), (3, ext, 4097, big, np.zeros(4097), "own"),
         (3, ext, 2, np.array([[1, 3, 0], [2, 4, 0]], np.uint8), out, "own"),   # a code above 3
         (3, ext, 2, np.array([[1, 3, 0], [0, 255, 0]], np.uint8), out, "own"),

@@ -233,6 +233,7 @@ def test_refusals_through_the_c_abi():
         (3, np.array([2, 2, 2047], np.int64), 2, ops, cs, d, host, "own"),                # a wrong product
         (2, ext, 2, ops, cs, d, host, "own"),
         (3, np.array([2, 2, 0], np.int64), 2, ops, cs, d, host, "own"),
+        (3, np.array([2 ** 21, 2 ** 21, 2], np.int64), 2, ops, cs, d, host, "own"),       # past 2^40 elements before the last axis
         (3, ext, -1, ops, cs, d, host, "own"), (3, ext, 4097, big, np.ones(4097), d, host, "own"),
         (3, ext, 2, np.array([[1, 3, 0], [2, 4, 0]], np.uint8), cs, d, host, "own"),      # a code above 3
         (3, ext, 2, np.array([[1, 3, 0], [0, 0, 1]], np.uint8), cs, d, host, "own"),      # a letter on an axis of extent 2048

@@ -226,6 +226,12 @@ def test_refusals():
     for bad_ext, bad_keep in (([n // 2, 3], [1, 0]), ([n], [2]), ([n, 0], [1, 1]), ([n], [-1])):
         with pytest.raises(ValueError):
             ex.rdm_result(bad_ext, bad_keep)
+    # extents whose running product passes 2^40 elements before the last axis
+    ext, kp = np.array([2 ** 21, 2 ** 21, 2], np.int64), np.array([0, 0, 1], np.int32)
+    out = np.full((2, 2), 7.0 + 7.0j, np.complex128)
+    rc = runtime.load().ctg_exec_result_rdm(ex.handle, 3, ext.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            kp.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(out.ctypes.data))
+    assert rc == -1 and runtime.load().ctg_last_error() and np.all(out == 7.0 + 7.0j)
     assert ex.device_bytes() == before                            # (not even the scratch was allocated)
     du.check_rdm(ex.rdm_result((64, 128), [1, 0]), x, (64, 128), [0])
     assert ex.device_bytes() > before

@@ -6,6 +6,7 @@ Data reaches the result tensor bit for bit through a one-tensor tree (a single c
 tests/test_gpu_sample.py.  The references and the tolerance of a marginal are in tests/reduce_util.py: top-k is
 compared exactly, a marginal within ``2 t 2^-53`` of the reference per output (t elements per output), which is
 derived from the error of two summation orders and never from what the device returns."""
+import ctypes as C
 import itertools
 import os
 
@@ -13,7 +14,7 @@ import numpy as np
 import pytest
 
 import cotengra_amd as ca
-from cotengra_amd import circuits
+from cotengra_amd import circuits, runtime
 from cotengra_amd.contractor import _tree_contractor
 
 import reduce_util as ru
@@ -267,6 +268,13 @@ def test_marginal_bad_arguments_raise():
     for ext, keep in (([B, 5], [1, 0]), ([B + 5], [2]), ([B + 5, 0], [1, 1]), ([B + 5], [-1])):
         with pytest.raises(ValueError):
             ex.marginal_result(ext, keep)
+    # extents whose running product passes 2^40 elements before the last axis: refused by the library itself
+    before = ex.device_bytes()
+    ext, kp = np.array([2 ** 21, 2 ** 21, 2], np.int64), np.array([0, 0, 1], np.int32)
+    out = np.full(2, 7.0)
+    rc = runtime.load().ctg_exec_result_marginal(ex.handle, 3, ext.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 kp.ctypes.data_as(C.POINTER(C.c_int32)), out.ctypes.data_as(C.POINTER(C.c_double)))
+    assert rc == -1 and runtime.load().ctg_last_error() and np.all(out == 7.0) and ex.device_bytes() == before
     assert ex.download_result().tobytes() == x.tobytes()
 
 
