@@ -18,7 +18,7 @@ from .utils import (  # noqa: F401
 
 __version__ = "0.1.0"
 from . import interface, plan  # noqa: F401,E402
-from .contractor import ExpectationResult, HipContractor, MarginalResult, RdmResult, TopKResult, make_contractor  # noqa: F401,E402
+from .contractor import ExpectationResult, HipContractor, MarginalResult, RdmResult, RdmWideResult, TopKResult, make_contractor  # noqa: F401,E402
 from .contractor import ApplyResult, EnergyResult  # noqa: F401,E402
 from .contractor import operator_requests, pauli_requests  # noqa: F401,E402
 from .interface import (  # noqa: F401,E402

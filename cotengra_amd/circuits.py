@@ -415,6 +415,111 @@ def reduced_density_matrix(n, gates, qubits, fixed=None, optimize="greedy", dtyp
     return res.rho / res.norm, res.norm
 
 
+ENTANGLEMENT_MAX_QUBITS = 12   # the smaller side of a cut: D = 4096 rows (Executor.RDM_WIDE_MAX_DIM)
+
+
+def entanglement_cut(n, qubits, fixed=None):
+    """The side of the cut ``qubits | the other open qubits`` whose reduced density matrix ``entanglement_spectrum``
+    computes -- host only: ``(side, open_qubits, fixed)``.  The two sides of a pure state share their non-zero
+    spectrum, so the SMALLER one is taken (``qubits`` itself on a tie), in ascending order when it is the
+    complement.  ``ValueError`` for what ``reduced_density_matrix`` refuses of ``qubits`` and ``fixed``, and for a
+    smaller side above ``ENTANGLEMENT_MAX_QUBITS`` qubits."""
+    n = int(n)
+    qs = [int(q) for q in qubits]
+    _check_marginal(n, qs)
+    fixed = {int(q): int(b) for q, b in (fixed or {}).items()}
+    for q, b in fixed.items():
+        if q < 0 or q >= n:
+            raise ValueError(f"fixed: qubit {q} outside the {n} qubits.")
+        if b not in (0, 1):
+            raise ValueError(f"fixed: qubit {q} is projected onto {b}; 0 or 1 is expected.")
+        if q in qs:
+            raise ValueError(f"qubit {q} is both fixed and kept.")
+    open_qubits = [q for q in range(n) if q not in fixed]
+    rest = [q for q in open_qubits if q not in qs]
+    side = rest if len(rest) < len(qs) else qs
+    if len(side) > ENTANGLEMENT_MAX_QUBITS:
+        raise ValueError(f"the smaller side of the cut has {len(side)} qubits; at most {ENTANGLEMENT_MAX_QUBITS} "
+                         f"(a matrix of {1 << ENTANGLEMENT_MAX_QUBITS} rows).")
+    return side, open_qubits, fixed
+
+
+def _cut_result(n, gates, qubits, fixed, optimize, dtype, target_size, matrix):
+    """The (wide) reduced density matrix result of the smaller side of the cut, and the number of its rows."""
+    from .interface import array_contract_tree
+    from .runtime import Executor
+
+    side, open_qubits, fixed = entanglement_cut(n, qubits, fixed)
+    template = "".join(str(fixed[q]) if q in fixed else "?" for q in range(n))
+    inputs, output, size_dict, arrays = circuit_to_network(n, gates, template, simplify=True, dtype=dtype)
+    tree = array_contract_tree(inputs, output, size_dict, optimize=optimize)
+    if [tuple(t) for t in tree.inputs] != [tuple(t) for t in inputs] or tuple(tree.output) != tuple(output):
+        raise ValueError("optimize: the tree is not over this circuit's network.")
+    if target_size is not None:
+        tree = tree.slice(target_size=target_size)
+    label = dict(zip(open_qubits, output))   # (one output index per open qubit, in qubit order)
+    keep = [label[q] for q in side]
+    d = 1 << len(side)
+    if d <= Executor.RDM_MAX_DIM:
+        res = tree.contract_rdm(arrays, keep)
+    else:
+        res = tree.contract_rdm_wide(arrays, keep, matrix=matrix)
+    if not res.norm > 0:
+        raise ValueError("the state has norm zero.")
+    return res, d
+
+
+def _cut_spectrum(rho, d):
+    """The eigenvalues of the Hermitian ``rho`` descending, scaled to sum 1: ``ValueError`` for one below
+    ``-D 2^-52 max``, the rest clipped at 0."""
+    w = np.linalg.eigvalsh(rho)[::-1]
+    top = float(w[0])
+    if float(w[-1]) < -d * 2.0 ** -52 * top:
+        raise ValueError(f"the reduced density matrix has the eigenvalue {float(w[-1])!r} (largest: {top!r}): it is "
+                         "not positive semidefinite within rounding.")
+    w = np.clip(w, 0.0, None)
+    return w / w.sum()
+
+
+def entanglement_spectrum(n, gates, qubits, fixed=None, optimize="greedy", dtype="complex64", target_size=None):
+    """The entanglement spectrum of the cut ``qubits | the other open qubits`` of the output state of the
+    ``n``-qubit circuit ``gates`` (``fixed``: as for :func:`reduced_density_matrix`): the eigenvalues of the reduced
+    density matrix of the smaller side (:func:`entanglement_cut`), which is formed on the device --
+    ``ContractionTree.contract_rdm`` up to 6 qubits, ``contract_rdm_wide`` up to 12 -- and
+    diagonalised on the host by ``numpy.linalg.eigvalsh``.
+
+    Returns ``(eigenvalues, norm)``: the ``2^k`` eigenvalues descending, summing to 1, and ``norm`` = ``sum
+    |amplitude|^2`` of the open qubits.  ``ValueError`` for what :func:`entanglement_cut` refuses, a state of norm
+    zero and an eigenvalue below ``-D 2^-52 max``."""
+    res, d = _cut_result(n, gates, qubits, fixed, optimize, dtype, target_size, True)
+    return _cut_spectrum(res.rho, d), res.norm
+
+
+def entanglement_entropy(n, gates, qubits, fixed=None, alpha=1, base=2, optimize="greedy", dtype="complex64",
+                         target_size=None):
+    """The entanglement entropy across the cut ``qubits | the other open qubits``: von Neumann, ``-sum l log l``, for
+    ``alpha = 1``; Renyi, ``log(sum l^alpha) / (1 - alpha)``, otherwise; logarithms to ``base``.  ``alpha = 2``
+    needs no eigenvalues: ``-log(purity / norm^2)`` with the purity ``sum |rho[a, b]|^2`` summed on the device -- above
+    6 qubits on the smaller side the matrix is not downloaded at all (``contract_rdm_wide(matrix=False)``).
+
+    Returns ``(entropy, norm)``.  ``ValueError`` for ``alpha <= 0``, ``base <= 1`` and what
+    :func:`entanglement_spectrum` refuses."""
+    alpha, base = float(alpha), float(base)
+    if not alpha > 0:
+        raise ValueError(f"alpha = {alpha}: a positive order is expected.")
+    if not base > 1:
+        raise ValueError(f"base = {base}: a base above 1 is expected.")
+    res, d = _cut_result(n, gates, qubits, fixed, optimize, dtype, target_size, alpha != 2.0)
+    if alpha == 2.0:
+        purity = res.purity if hasattr(res, "purity") else float(np.sum(np.abs(res.rho) ** 2))
+        return float(-np.log(purity / res.norm ** 2) / np.log(base)), res.norm
+    w = _cut_spectrum(res.rho, d)
+    if alpha == 1.0:
+        nz = w[w > 0]
+        return float(-np.sum(nz * np.log(nz)) / np.log(base)), res.norm
+    return float(np.log(np.sum(w ** alpha)) / (1.0 - alpha) / np.log(base)), res.norm
+
+
 def _circuit_pauli_requests(who, n, paulis, fixed, coeffs):
     """The validation ``pauli_expectation`` and ``energy_gradient`` share -- host only: ``(n, fixed, several?,
     [{qubit: letter}, ...] without identities, coeffs as float64 or None)``."""

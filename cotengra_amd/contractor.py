@@ -312,6 +312,16 @@ class RdmResult(collections.namedtuple("RdmResult", "rho dims norm exponent")):
     __slots__ = ()
 
 
+class RdmWideResult(collections.namedtuple("RdmWideResult", "rho dims purity norm exponent")):
+    """What ``HipContractor.rdm_wide`` returns: ``rho`` the ``(D, D)`` reduced density matrix of the kept output
+    indices, ``64 < D <= 4096``, as :class:`RdmResult` describes it, or ``None`` with ``matrix=False``; ``dims`` the
+    kept extents in the caller's order; ``purity`` = ``sum |rho[a, b]|^2`` summed on the device, raw: divide by
+    ``norm ** 2``; ``norm`` = ``sum |x|^2`` of the whole result; the base-10 ``exponent`` taken out under
+    ``strip_exponent`` (0.0 otherwise: true values are ``rho 10^(2 exponent)``, ``purity 10^(4 exponent)``)."""
+
+    __slots__ = ()
+
+
 def _marginal_requests(tree, keep):
     """``keep`` of ``HipContractor.marginal`` as ``(several?, [(labels, keep flags per output axis, shape in the
     tensor's order, permutation to the caller's order), ...])`` -- host only; ``ValueError`` for a label that is
@@ -1253,6 +1263,37 @@ class HipContractor:
             norm = ex.sample_info()[0]
             exponent = ex.get_exponent()[0] if strip else 0.0
         return RdmResult(rho=rhos if several else rhos[0], dims=dims if several else dims[0], norm=norm, exponent=exponent)
+
+    def rdm_wide(self, *arrays, keep, matrix=True, strip_exponent=False, check_zero=False, reuse=False):
+        """:meth:`rdm` for kept extents whose product ``D`` is above 64 and at most 4096 -- the smaller side of a cut
+        of the whole system -- tiled over the lower triangle on the device (``ctg_exec_result_rdm_wide``, DESIGN.md
+        section 20).  ``keep``: ONE sequence of output index labels; a list of requests is a ``ValueError`` (a matrix
+        of up to 256 MiB per request is not a batch).  Rows and columns are row-major over the labels in the order
+        they were named.  ``matrix=False``: ``rho`` is ``None`` and only ``purity = sum |rho[a, b]|^2`` comes back
+        from the device, the same bits as with the matrix.  Returns an :class:`RdmWideResult`.  ``ValueError`` --
+        before the device is touched -- for what :meth:`rdm` refuses of the labels and for ``D`` outside ``65 ..
+        4096`` (up to 64 it is :meth:`rdm`'s).  Leaves a result that ``reuse=True`` can read, and takes
+        ``reuse=True`` as :meth:`topk` does.  Not differentiable."""
+        several, reqs = _marginal_requests(self.tree, keep)
+        if several:
+            raise ValueError("rdm_wide: one request per call; a list of requests was given.")
+        labels, flags, kshape, perm = reqs[0]
+        shape = tuple(self.tree.gathered_shape())
+        runtime.rdm_wide_dim(shape, flags)
+        if reuse and arrays:
+            raise ValueError("reuse=True reads the result of the call before: give no arrays.")
+        with self._lock:
+            st, strip = self._reduce_state(arrays, strip_exponent, check_zero, reuse)
+            ex = st["exec"]
+            rho, purity = ex.rdm_wide_result(shape, flags, matrix=matrix)
+            if rho is not None:
+                d = rho.shape[0]
+                # rows and columns from the tensor's order of the kept axes to the caller's
+                rho = rho.reshape(kshape + kshape).transpose(perm + tuple(len(perm) + p for p in perm))
+                rho = np.array(rho.reshape(d, d), order="C")
+            norm = ex.sample_info()[0]
+            exponent = ex.get_exponent()[0] if strip else 0.0
+        return RdmWideResult(rho=rho, dims=tuple(kshape[p] for p in perm), purity=purity, norm=norm, exponent=exponent)
 
     def expectation(self, *arrays, paulis, strip_exponent=False, check_zero=False, reuse=False):
         """Contract (all slices, as a call does) and return ``<x| P |x> = sum over j of conj(x[j]) (P x)[j]`` of the

@@ -251,6 +251,16 @@ class ContractExpression:
         self._after_reduce()
         return out
 
+    def rdm_wide(self, *arrays, keep, **kwargs):
+        """``expr(*arrays)`` followed by the reduced density matrix of the output indices ``keep`` (65 .. 4096 rows)
+        and its purity on the device (``HipContractor.rdm_wide``); the expression's own ``strip_exponent`` /
+        ``check_zero`` unless given."""
+        kwargs.setdefault("strip_exponent", self.fn.strip_exponent)
+        kwargs.setdefault("check_zero", self.fn.check_zero)
+        out = self.fn.rdm_wide(*arrays, keep=keep, **kwargs)
+        self._after_reduce()
+        return out
+
     def expectation(self, *arrays, paulis, **kwargs):
         """``expr(*arrays)`` followed by the expectation values of the Pauli strings ``paulis`` over the output
         indices on the device (``HipContractor.expectation``); the expression's own ``strip_exponent`` /

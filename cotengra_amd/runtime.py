@@ -6,6 +6,7 @@ raises immediately -- there is no CPU fallback anywhere in the package.
 
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import operator
 import os
@@ -56,6 +57,8 @@ SYMBOLS = (
     "ctg_exec_result_topk",
     "ctg_exec_result_marginal",
     "ctg_exec_result_rdm",
+    "ctg_exec_result_rdm_wide",
+    "ctg_rdm_wide_plan",
     "ctg_exec_result_pauli",
     "ctg_exec_result_pauli_apply",
     "ctg_exec_result_op_apply",
@@ -179,6 +182,8 @@ def load():
         "ctg_exec_result_topk": [vp, C.c_int64, i64p, vp, C.POINTER(C.c_double)],
         "ctg_exec_result_marginal": [vp, C.c_int64, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_double)],
         "ctg_exec_result_rdm": [vp, C.c_int64, i64p, C.POINTER(C.c_int32), vp],
+        "ctg_exec_result_rdm_wide": [vp, C.c_int64, i64p, C.POINTER(C.c_int32), vp, C.POINTER(C.c_double)],
+        "ctg_rdm_wide_plan": [C.c_int32, C.c_int64, i64p, C.POINTER(C.c_int32), i64p],
         "ctg_exec_result_pauli": [vp, C.c_int64, i64p, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_double)],
         "ctg_exec_result_pauli_apply": [vp, C.c_int64, i64p, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_double), vp, vp],
         "ctg_exec_result_op_apply": [vp, C.c_int64, i64p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -280,6 +285,118 @@ def rdm_variant(dtype, extents, keep):
 
 
 _DTYPE_TAG = {"float32": "float", "float64": "double", "complex64": "c64", "complex128": "c128"}
+_DTYPE_CODE = {"float32": 0, "float64": 1, "complex64": 2, "complex128": 3}   # CTG_F32 .. CTG_C128
+
+
+def rdm_wide_dim(extents, keep):
+    """``D``, the product of the kept extents of a wide reduced-density-matrix request: ``ValueError`` for an extent
+    below 1, for ``D`` up to ``Executor.RDM_MAX_DIM`` (those are ``rdm_result``'s: one route per ``D``) and for ``D``
+    above ``Executor.RDM_WIDE_MAX_DIM`` -- host only, before any device work."""
+    d = 1
+    for n, f in zip(extents, keep):
+        if n < 1:
+            raise ValueError(f"extent {n} is not positive.")
+        if f == 1:
+            d *= int(n)
+    if d <= Executor.RDM_MAX_DIM:
+        raise ValueError(f"rdm_wide: the kept extents' product is {d}; up to {Executor.RDM_MAX_DIM} (CTG_RDM_MAX_DIM) "
+                         "it is rdm_result (ctg_exec_result_rdm) that computes the matrix.")
+    if d > Executor.RDM_WIDE_MAX_DIM:
+        raise ValueError(f"rdm_wide: the kept extents' product is {d}; at most {Executor.RDM_WIDE_MAX_DIM} "
+                         "(CTG_RDM_WIDE_MAX_DIM).")
+    return d
+
+
+RdmWidePlan = collections.namedtuple(
+    "RdmWidePlan", "route dim edge panels blocks splits cols chunks grid scratch_bytes name_code")
+RdmWidePlan.__doc__ = """The words of ``ctg_rdm_wide_plan`` (include/ctg_hip.h): ``route`` 0 power of two, 1 general;
+``dim`` = D; ``edge`` rows of a row panel; ``panels``; ``blocks`` of the lower triangle (block ``bi (bi + 1) / 2 + bj`` is
+panel ``bi`` times panel ``bj``); ``splits`` along r (split ``s`` takes the chunks ``s chunks / splits`` up to
+``(s + 1) chunks / splits``); ``cols`` values of r per chunk; ``chunks``; ``grid`` = blocks * splits; ``scratch_bytes``;
+``name_code`` = 4 * route + dtype code."""
+
+
+def rdm_wide_scratch_bound(d):
+    """``CTG_RDM_WIDE_SCRATCH_BYTES(D)`` of include/ctg_hip.h."""
+    return 16 * d * d + max(8 * d * d + 512 * d, 64 << 20) + (64 << 10)
+
+
+def _lowest_bits(mask, k):
+    r = 0
+    while k > 0 and mask:
+        r |= mask & -mask
+        mask &= mask - 1
+        k -= 1
+    return r
+
+
+def rdm_wide_plan(dtype, extents, keep):
+    """What ``ctg_exec_result_rdm_wide`` launches for a result of ``dtype`` and shape ``extents`` with the axes ``keep``
+    kept, as an :class:`RdmWidePlan` -- a pure-Python mirror of ``ctg_rdm_wide_plan`` (csrc/ctg_rdm_wide.hip), word for
+    word.  ``ValueError`` for what :func:`rdm_wide_dim` refuses and for a keep entry outside {0, 1}."""
+    name = np.dtype(dtype).name
+    code = _DTYPE_CODE[name]
+    p = 2 if code >= 2 else 1
+    ext = [int(v) for v in extents]
+    kp = [int(f) for f in keep]
+    if len(ext) != len(kp):
+        raise ValueError(f"{len(ext)} extents and {len(kp)} keep entries.")
+    for v, f in zip(ext, kp):
+        if v < 1:
+            raise ValueError(f"extent {v} is not positive.")
+        if f not in (0, 1):
+            raise ValueError("rdm_wide: a keep entry is neither 0 nor 1")
+    d = rdm_wide_dim(ext, kp)
+    n = 1
+    for v in ext:
+        n *= v
+    if n > 1 << 40:
+        raise ValueError("rdm_wide: the extents' product does not equal result_elems")
+    t = n // d
+    up256 = lambda b: (b + 255) & ~255   # noqa: E731
+    pieces = (d * d + 4095) // 4096
+    if n >= 4096 and all(v & (v - 1) == 0 for v in ext):
+        route, edge = 0, 64
+        mask, stride = 0, 1
+        for v, f in zip(reversed(ext), reversed(kp)):
+            if f:
+                mask |= (v - 1) * stride
+            stride *= v
+        r = (n - 1) & ~mask
+        rlo = _lowest_bits(r, 5)
+        cols = 1 << bin(rlo).count("1")
+        chunks = 1 << bin(r & ~rlo).count("1")
+        panels = d // edge
+        blocks = panels * (panels + 1) // 2
+        splits = 1
+        while blocks * splits < 512 and 2 * splits * 32 <= chunks:
+            splits *= 2
+        grid = blocks * splits
+        part = grid * edge * edge * p * 8
+    else:
+        route, edge, panels = 1, 1, d
+        blocks = d * (d + 1) // 2
+        chunk = max(1024, (t + 1023) // 1024)
+        cap = max(1, (64 << 20) // (blocks * p * 8))
+        if (t + chunk - 1) // chunk > cap:
+            chunk = (t + cap - 1) // cap
+        cols = chunk
+        chunks = (t + chunk - 1) // chunk
+        splits = chunks
+        grid = blocks * splits
+        part = grid * p * 8
+    scratch = up256(d * d * p * 8) + up256(part) + up256(pieces * 8) + up256(8)
+    return RdmWidePlan(route, d, edge, panels, blocks, splits, cols, chunks, grid, scratch, 4 * route + code)
+
+
+def rdm_wide_variant(dtype, extents, keep):
+    """The kernel ``ctg_exec_result_rdm_wide`` chooses for a result of ``dtype`` and shape ``extents`` with the axes
+    ``keep`` kept (csrc/ctg_rdm_wide.hip): ``"rdm_wide_kernel<T,64>"`` on the power-of-two route (every extent a power
+    of two, at least 4096 elements; 64 the block edge), ``"rdm_wide_general_kernel<T>"`` otherwise; ``T`` one of
+    ``float``, ``double``, ``c64``, ``c128``."""
+    plan = rdm_wide_plan(dtype, extents, keep)
+    t = _DTYPE_TAG[np.dtype(dtype).name]
+    return f"rdm_wide_kernel<{t},{plan.edge}>" if plan.route == 0 else f"rdm_wide_general_kernel<{t}>"
 
 
 def _pauli_ops(extents, ops):
@@ -817,6 +934,32 @@ class Executor:
     def rdm_variant(self, extents, keep):
         """The name of the kernel ``rdm_result(extents, keep)`` runs on this executor (:func:`rdm_variant`)."""
         return rdm_variant(self.plan.dtype, extents, keep)
+
+    # -- reduced density matrices above RDM_MAX_DIM rows (csrc/ctg_rdm_wide.hip) -- #
+
+    RDM_WIDE_MAX_DIM = 4096   # CTG_RDM_WIDE_MAX_DIM
+
+    def rdm_wide_result(self, extents, keep, matrix=True):
+        """``(rho, purity)`` of the result tensor for ``RDM_MAX_DIM < D <= RDM_WIDE_MAX_DIM`` kept values
+        (``ctg_exec_result_rdm_wide``): ``rho`` as :meth:`rdm_result` defines it, or ``None`` with ``matrix=False``
+        (nothing of the matrix is downloaded); ``purity = sum |rho[a, b]|^2`` summed in a fixed order on the device, not
+        normalised, the same bits either way.  ``ValueError`` for what ``marginal_result`` refuses, for ``D`` outside
+        that range (nothing is launched) and for a result whose ``sum p`` is not finite."""
+        ext = np.ascontiguousarray(extents, dtype=np.int64).reshape(-1)
+        kp = np.ascontiguousarray(keep, dtype=np.int32).reshape(-1)
+        if ext.size != kp.size:
+            raise ValueError(f"{ext.size} extents and {kp.size} keep entries.")
+        d = rdm_wide_dim(ext.tolist(), kp.tolist())
+        cplx = np.dtype(self.plan.dtype).kind == "c"
+        out = np.empty((d, d), dtype=np.complex128 if cplx else np.float64) if matrix else None
+        purity = C.c_double()
+        _check(load().ctg_exec_result_rdm_wide(self.handle, ext.size, _i64p(ext), kp.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               C.c_void_p(out.ctypes.data if matrix else None), C.byref(purity)))
+        return out, purity.value
+
+    def rdm_wide_variant(self, extents, keep):
+        """The name of the kernel ``rdm_wide_result(extents, keep)`` runs on this executor (:func:`rdm_wide_variant`)."""
+        return rdm_wide_variant(self.plan.dtype, extents, keep)
 
     # -- expectation values of Pauli strings over the result tensor (csrc/ctg_pauli.hip) -- #
 

@@ -1102,6 +1102,14 @@ class ContractionTree:
 
         return _tree_contractor(self, order).rdm(*arrays, keep=keep, **kwargs)
 
+    def contract_rdm_wide(self, arrays, keep, order=None, **kwargs):
+        """:meth:`contract` followed by the reduced density matrix of the output indices ``keep`` (one sequence of
+        labels whose extents multiply to 65 .. 4096) and its purity on the device (``HipContractor.rdm_wide``;
+        ``kwargs``: ``matrix``, ``strip_exponent``, ``check_zero``, ``reuse``).  Not differentiable."""
+        from .contractor import _tree_contractor
+
+        return _tree_contractor(self, order).rdm_wide(*arrays, keep=keep, **kwargs)
+
     def contract_expectation(self, arrays, paulis, order=None, **kwargs):
         """:meth:`contract` followed by the expectation values ``<x| P |x>`` of the Pauli strings ``paulis`` over
         the output indices (a string over ``IXYZ``, a mapping ``{label: letter}``, a sequence of ``(label, letter)``

@@ -668,6 +668,57 @@ int ctg_exec_result_pauli_apply(ctg_exec* exec, int64_t rank, const int64_t* ext
 #define CTG_OP_MAX_ENTRIES (1 << 20)
 int ctg_exec_result_op_apply(ctg_exec* exec, int64_t rank, const int64_t* extents, int64_t m, const int32_t* naxes,
                              const int32_t* axes, const double* mats, void* dev_out, void* host_out);
+/* Added to ABI 10 WITHOUT a bump of CTG_ABI_VERSION likewise (two new symbols; a binding that needs them looks them up):
+ * reduced density matrices of 65 .. CTG_RDM_WIDE_MAX_DIM rows of the result tensor on the device
+ * (csrc/ctg_rdm_wide.hip): the cut of a 20 - 24 qubit state or a 12 - 14 site spin-1 chain.
+ *   rho[a, b] = sum over r of x[a, r] * conj(x[b, r])
+ * with extents, keep, D, t, the layout of out and the reading of the tensor exactly those of ctg_exec_result_rdm
+ * (whoever owns the memory, the mantissa under strip_exponent, after the stream's earlier work, after the statistics
+ * passes, which run first; the stream is synchronised; CTG_E_NORM when sum p is not finite; an all-zero tensor gives a
+ * zero matrix and purity 0).  out (D * D double2, or double for real plans) may be NULL, and so may purity, not both:
+ *   *purity = sum over a, b of |rho[a, b]|^2,
+ * a fixed-order fp64 sum over the finished matrix on the device (pieces of 4096 entries, a lane's 16 in ascending
+ * order, a tree over the 256 lanes, the pieces likewise): with out == NULL the Renyi-2 entropy of a 4096-row cut needs
+ * no 256 MiB download.  NOT normalised: the caller divides by (sum p)^2.
+ * CTG_E_INVALID -- from one prologue, before anything is allocated or launched -- for a null exec, out and purity both
+ * null, everything ctg_exec_result_marginal refuses, D > CTG_RDM_WIDE_MAX_DIM, and D <= CTG_RDM_MAX_DIM: that matrix is
+ * ctg_exec_result_rdm's, one route per D, so its bits never depend on the entry that was called.
+ *   - Exactly Hermitian: only b <= a is computed, the other half is written as its conjugate, Im rho[a, a] = 0.0.
+ *   - Every product and sum is fp64 (v_mfma_f64_16x16x4_f64 on the power-of-two route); no floating-point atomics;
+ *     every grid, split and association of a sum is a function of (dtype, extents, keep) alone.  The error bound per
+ *     real component is that of ctg_exec_result_rdm.
+ * ctg_rdm_wide_plan (host only, touches no device) returns what ctg_exec_result_rdm_wide launches for a result of
+ * `dtype` (CTG_F32 .. CTG_C128) whose extents' product stands for result_elems, the same refusals included:
+ *   words[0] route        0: power of two (every extent a power of two, at least 4096 elements), 1: general
+ *   words[1] D
+ *   words[2] edge         rows of a row panel: 64 (general: 1)
+ *   words[3] panels       D / edge; row a is row a % edge of panel a / edge
+ *   words[4] blocks       panels (panels + 1) / 2 of the lower triangle: block bi (bi + 1) / 2 + bj is panel bi x panel bj
+ *   words[5] splits       along r: split s takes the chunks s * chunks / splits .. (s + 1) * chunks / splits - 1
+ *   words[6] cols         values of r in a chunk (r row-major over the dropped axes): min(32, t); general: see below
+ *   words[7] chunks       ceil(t / cols)
+ *   words[8] grid         blocks * splits: workgroups of the tile kernel (general: work items, 256 to a workgroup)
+ *   words[9] scratch      bytes of the executor's scratch the call lays out, at most CTG_RDM_WIDE_SCRATCH_BYTES(D)
+ *   words[10] name        4 * route + dtype: "rdm_wide_kernel<T,64>" | "rdm_wide_general_kernel<T>", T in
+ *                         float | double | c64 | c128
+ * Power of two: workgroup (block, split) reads the one or two 64-row panels of its block chunk by chunk in ascending
+ * order (16-byte loads, the next chunk's in flight), widens them to fp64 in LDS and keeps the block's 64 x 64 entries
+ * in registers; a diagonal block computes its lower 16 x 16 tiles only.  splits doubles while blocks * splits < 512
+ * and a split keeps at least 32 chunks; a finish kernel adds the splits' partials in ascending order and mirrors.
+ * General: a serial walk per (pair a >= b, chunk of r), chunks of max(1024, ceil(t / 1024)) values, longer where the
+ * per-chunk sums would pass 64 MiB; the chunks are added in ascending order; not tuned.
+ * Scratch: the buffer of ctg_exec_result_topk (counted by ctg_exec_device_bytes, freed by ctg_exec_destroy): 16 D^2 bytes
+ * for the matrix, 64 KiB of partials per (block, split) -- 8 D^2 + 512 D bytes when splits = 1, less than 64 MiB
+ * otherwise -- and 8 bytes per 4096 entries for the purity: 387 MiB at D = 4096.  Not differentiable; no multi-rank
+ * entry, as above. */
+#define CTG_RDM_WIDE_MAX_DIM 4096
+#define CTG_RDM_WIDE_PLAN_WORDS 11
+#define CTG_RDM_WIDE_SCRATCH_BYTES(D)                                                                                  \
+    (16ll * (D) * (D) + (8ll * (D) * (D) + 512ll * (D) > (64ll << 20) ? 8ll * (D) * (D) + 512ll * (D) : (64ll << 20)) + \
+     (64ll << 10))
+int ctg_exec_result_rdm_wide(ctg_exec* exec, int64_t rank, const int64_t* extents, const int32_t* keep, void* out,
+                             double* purity);
+int ctg_rdm_wide_plan(int32_t dtype, int64_t rank, const int64_t* extents, const int32_t* keep, int64_t* words);
 /* debugging aid: copy `n` elements of the arena starting at element `offset`
  * to the host (synchronous) */
 int ctg_exec_download_arena(ctg_exec* exec, int64_t offset, int64_t n, void* host_out);

@@ -13,7 +13,7 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ["ctg_sample.hip", "ctg_reduce.hip", "ctg_rdm.hip", "ctg_pauli.hip", "ctg_pauli_apply.hip", "ctg_op_apply.hip"]
+SOURCES = ["ctg_sample.hip", "ctg_reduce.hip", "ctg_rdm.hip", "ctg_rdm_wide.hip", "ctg_pauli.hip", "ctg_pauli_apply.hip", "ctg_op_apply.hip"]
 FIELDS = [("VGPRs", "vgpr"), ("AGPRs", "agpr"), ("TotalSGPRs", "sgpr"), ("ScratchSize [bytes/lane]", "scratch"),
           ("LDS Size [bytes/block]", "lds"), ("Occupancy [waves/SIMD]", "occ")]
 
@@ -21,6 +21,8 @@ FIELDS = [("VGPRs", "vgpr"), ("AGPRs", "agpr"), ("TotalSGPRs", "sgpr"), ("Scratc
 def remarks(csrc, src):
     """{kernel: figures} of one source, and its device assembly without comments and the compilation unit's id"""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not os.path.exists(os.path.join(csrc, src)):   # (a source the revision does not have yet)
+        return {"": None}
     with tempfile.NamedTemporaryFile(suffix=".s") as asm:
         err = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-S", src,
                               "-o", asm.name, "-Rpass-analysis=kernel-resource-usage"], cwd=csrc, check=True,
