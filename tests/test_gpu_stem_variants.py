@@ -19,6 +19,9 @@ integer  every input -- the state, the (3, 3) gate, the small operands -- has re
          fp16 x 2 leaves out, second limb x second limb, is zero.  So no rounding happens anywhere, in any form, and
          what differs from the oracle is a missing chunk, a wrong item or column group, a stale LDS plane, a wrong
          limb pairing or a lost store -- most of which the 1e-5 gate cannot see (a dropped limb product is 2^-22).
+         What this data cannot see either: the planes of the second and third limbs of B1, B2 and the state hold
+         zeros, so a product that pairs them wrongly reads zeros where zeros are expected.  Operands with every limb
+         populated, still bit for bit: tests/test_gpu_limb_probes.py.
 
 Running tensors of 2^15 to 2^18 elements: fewer than 256 tiles, one pass of every workgroup's loop.  The deep rows run
 512 and 1024 tiles (two and four per workgroup: the steady state, asserted from the plan) for the loop structures that
