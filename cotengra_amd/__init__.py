@@ -21,6 +21,7 @@ from . import interface, plan  # noqa: F401,E402
 from .contractor import ExpectationResult, HipContractor, MarginalResult, RdmResult, RdmWideResult, TopKResult, make_contractor  # noqa: F401,E402
 from .contractor import ApplyResult, EnergyResult  # noqa: F401,E402
 from .contractor import operator_requests, pauli_requests  # noqa: F401,E402
+from .contractor import SpectrumResult, spectrum_requests  # noqa: F401,E402
 from .interface import (  # noqa: F401,E402
     array_contract,
     array_contract_expression,

@@ -603,6 +603,51 @@ def pauli_expectation(n, gates, paulis, fixed=None, coeffs=None, optimize="greed
     return out
 
 
+def z_correlations(n, gates, qubits=None, fixed=None, optimize="greedy", dtype="complex64", target_size=None):
+    """``<Z_i>``, ``<Z_i Z_j>`` and the connected correlations of the output state of the ``n``-qubit circuit
+    ``gates`` over ``qubits`` (default: every qubit not in ``fixed``), normalised: the cost function of a QAOA / Ising
+    problem with dense couplings, from ONE transform of the state on the device
+    (``ContractionTree.contract_pauli_spectrum`` with the ``k + k (k - 1) / 2`` strings selected; DESIGN.md section
+    21).  ``fixed``: a dict ``{qubit: 0 | 1}`` as for :func:`pauli_expectation`; a fixed qubit cannot be in ``qubits``.
+
+    Returns ``(z, zz, connected, norm)``: ``z[a] = <Z_qa>``, ``zz[a, b] = <Z_qa Z_qb>`` (symmetric, ones on the
+    diagonal), ``connected = zz - outer(z, z)``, all float64 and divided by ``norm`` = ``sum |amplitude|^2`` of the open
+    qubits.  ``ValueError`` -- before any device work -- for a qubit outside the circuit, repeated or fixed and for a
+    fixed value other than 0 / 1; and for a state of norm zero."""
+    from .interface import array_contract_tree
+
+    n, fixed, _, _, _ = _circuit_pauli_requests("z_correlations", n, [], fixed, None)
+    open_qubits = [q for q in range(n) if q not in fixed]
+    qs = open_qubits if qubits is None else [int(q) for q in qubits]
+    for q in qs:
+        if q < 0 or q >= n:
+            raise ValueError(f"z_correlations: qubit {q} outside the {n} qubits.")
+        if q in fixed:
+            raise ValueError(f"z_correlations: qubit {q} is fixed.")
+    if len(set(qs)) != len(qs):
+        raise ValueError("z_correlations: a qubit is named twice.")
+    template = "".join(str(fixed[q]) if q in fixed else "?" for q in range(n))
+    inputs, output, size_dict, arrays = circuit_to_network(n, gates, template, simplify=True, dtype=dtype)
+    tree = array_contract_tree(inputs, output, size_dict, optimize=optimize)
+    if [tuple(t) for t in tree.inputs] != [tuple(t) for t in inputs] or tuple(tree.output) != tuple(output):
+        raise ValueError("optimize: the tree is not over this circuit's network.")
+    if target_size is not None:
+        tree = tree.slice(target_size=target_size)
+    label = dict(zip(open_qubits, output))   # (one output index per open qubit, in qubit order)
+    k = len(qs)
+    pairs = [(a, b) for a in range(k) for b in range(a + 1, k)]
+    reqs = [{label[qs[a]]: "Z"} for a in range(k)] + [{label[qs[a]]: "Z", label[qs[b]]: "Z"} for a, b in pairs]
+    res = tree.contract_pauli_spectrum(arrays, flips=(), paulis=reqs)
+    if not res.norm > 0:
+        raise ValueError("z_correlations: the state has norm zero.")
+    values = np.asarray(res.values, dtype=np.float64) / res.norm
+    z = values[:k].copy()
+    zz = np.eye(k, dtype=np.float64)
+    for (a, b), v in zip(pairs, values[k:].tolist()):
+        zz[a, b] = zz[b, a] = v
+    return z, zz, zz - np.outer(z, z), res.norm
+
+
 def gate_derivatives(name, params=()):
     """``[dU / d params[0], ...]`` of :func:`gate_matrix`, analytic: one matrix for ``rz``, two for ``fs``, none for a
     gate without parameters."""

@@ -392,15 +392,18 @@ def pick_requests(tree, coords=None, indices=None):
 _PAULI_CODE = {"I": 0, "X": 1, "Y": 2, "Z": 3}
 
 
-def pauli_requests(tree, paulis):
+def pauli_requests(tree, paulis, max_requests=None):
     """``paulis`` of ``HipContractor.expectation`` as ``(several?, ops)`` with ``ops`` a uint8 array of shape
     ``(m, len(tree.output))`` over ``tree.gathered_shape()``: 0, 1, 2, 3 = I, X, Y, Z per output index -- host only.
     A request is a ``str`` of ``len(tree.output)`` letters over ``IXYZ`` (any case), one per output index in
     ``tree.output`` order; a mapping ``{label: letter}``; or a sequence of ``(label, letter)`` pairs; labels not named
     are I.  ``paulis`` is one request or a list of requests.  ``ValueError`` for an unknown or repeated label, a letter
     outside ``IXYZ``, a string of the wrong length, a letter other than I on an output index whose extent is not 2 and
-    more than ``Executor.PAULI_MAX_STRINGS`` requests."""
+    more than ``max_requests`` (default ``Executor.PAULI_MAX_STRINGS``) requests."""
     import collections.abc as cabc
+
+    if max_requests is None:
+        max_requests = runtime.Executor.PAULI_MAX_STRINGS
 
     output = list(tree.output)
     shape = tuple(int(d) for d in tree.gathered_shape())
@@ -424,8 +427,8 @@ def pauli_requests(tree, paulis):
     else:
         raise ValueError(f"paulis = {paulis!r}: give a string over IXYZ, a mapping {{label: letter}}, a sequence of "
                          "(label, letter) pairs, or a list of such requests.")
-    if len(reqs) > runtime.Executor.PAULI_MAX_STRINGS:
-        raise ValueError(f"paulis: {len(reqs)} requests; at most {runtime.Executor.PAULI_MAX_STRINGS} are taken by one call.")
+    if len(reqs) > max_requests:
+        raise ValueError(f"paulis: {len(reqs)} requests; at most {max_requests} are taken by one call.")
     ops = np.zeros((len(reqs), rank), dtype=np.uint8)
     for r, req in enumerate(reqs):
         if isinstance(req, str):
@@ -566,6 +569,54 @@ class ExpectationResult(collections.namedtuple("ExpectationResult", "values norm
     10^(2 exponent)``)."""
 
     __slots__ = ()
+
+
+class SpectrumResult(collections.namedtuple("SpectrumResult", "values norm exponent")):
+    """What ``HipContractor.pauli_spectrum`` returns: ``values`` the float64 values ``<x| P |x>``, NOT normalised --
+    without ``paulis`` an array of ``tree.gathered_shape()`` over ALL strings of the X / Y pattern ``flips`` (entry
+    ``b``: Y on the flipped axes where ``b`` is 1, X on the others, Z on the unflipped axes where ``b`` is 1; a tensor
+    on the device for ROCm torch inputs), with ``paulis`` one value per request in the caller's order (a 0-d float
+    for a single request); ``norm`` = ``sum |x|^2`` of the whole result; the base-10 ``exponent`` taken out under
+    ``strip_exponent`` (0.0 otherwise: true values are ``values 10^(2 exponent)``)."""
+
+    __slots__ = ()
+
+
+def spectrum_requests(tree, flips, paulis=None):
+    """``flips`` and ``paulis`` of ``HipContractor.pauli_spectrum`` as ``(flags, several?, select)`` -- host only:
+    ``flags`` 0 / 1 per output index of ``tree.gathered_shape()``, ``select`` the flat indices of the requested
+    strings in the spectrum (``None`` without ``paulis``).  ``ValueError`` for an output index of extent above 2, a
+    label of ``flips`` that is unknown, repeated or of extent 1, what :func:`pauli_requests` refuses (up to
+    ``Executor.PAULI_SPECTRUM_MAX_SELECT`` requests are taken) and a request whose X / Y letters are not exactly on
+    ``flips``."""
+    output = list(tree.output)
+    shape = tuple(int(d) for d in tree.gathered_shape())
+    for ix, d in zip(output, shape):
+        if d > 2:
+            raise ValueError(f"pauli_spectrum: output index {ix!r} has extent {d}; every extent must be 1 or 2.")
+    flags = [0] * len(output)
+    for ix in ([flips] if isinstance(flips, (str, bytes)) else list(flips)):
+        if ix not in output:
+            raise ValueError(f"flips: {ix!r} is not an output index of the tree (output: {output}).")
+        a = output.index(ix)
+        if flags[a]:
+            raise ValueError(f"flips: the label {ix!r} is named twice.")
+        if shape[a] != 2:
+            raise ValueError(f"flips: output index {ix!r} has extent {shape[a]}; only an index of extent 2 carries X or Y.")
+        flags[a] = 1
+    if paulis is None:
+        return flags, True, None
+    several, ops = pauli_requests(tree, paulis, max_requests=runtime.Executor.PAULI_SPECTRUM_MAX_SELECT)
+    flipped = (ops == 1) | (ops == 2)
+    wrong = np.flatnonzero((flipped != np.asarray(flags, dtype=bool)[None, :]).any(axis=1))
+    if wrong.size:
+        raise ValueError(f"paulis: request {int(wrong[0])} does not have its X / Y letters exactly on flips = "
+                         f"{[ix for ix, f in zip(output, flags) if f]}.")
+    stride = np.ones(len(shape), dtype=np.int64)
+    for a in range(len(shape) - 2, -1, -1):
+        stride[a] = stride[a + 1] * shape[a + 1]
+    select = (((ops == 2) | (ops == 3)).astype(np.int64) * stride[None, :]).sum(axis=1) if len(shape) else np.zeros(len(ops), np.int64)
+    return flags, several, np.ascontiguousarray(select, dtype=np.int64)
 
 
 class HipContractor:
@@ -1320,6 +1371,37 @@ class HipContractor:
                 norm = ex.result_stats()[0]
             exponent = ex.get_exponent()[0] if strip else 0.0
         return ExpectationResult(values=values if several else np.float64(values[0]), norm=norm, exponent=exponent)
+
+    def pauli_spectrum(self, *arrays, flips=(), paulis=None, strip_exponent=False, check_zero=False, reuse=False):
+        """Contract (all slices, as a call does) and return ``<x| P |x>`` for ALL Pauli strings that carry X or Y
+        exactly on the output indices ``flips`` (labels; none: all Z-type strings) -- one Walsh-Hadamard transform on
+        the device, ``2^L`` values for a few passes over the tensor where :meth:`expectation` takes one pass per 32
+        strings (``ctg_exec_result_pauli_spectrum``).  Every output index must have extent 1 or
+        2.  Without ``paulis``: ``values`` has ``tree.gathered_shape()``; entry ``b`` is the string with Y on the
+        flipped indices where ``b`` is 1 and X where 0, Z on the other indices where ``b`` is 1; numpy for numpy
+        inputs, a float64 tensor on the device for ROCm torch inputs.  With ``paulis`` (requests as for
+        :meth:`expectation`, up to 2^24): ``values[s]`` is the value of request ``s`` in the caller's order -- the same
+        quantity as :meth:`expectation`, in other bits; every request must have its X / Y exactly on ``flips``.
+        Values are NOT normalised: divide by ``norm``.  Returns a :class:`SpectrumResult`.  ``ValueError`` -- before
+        the device is touched -- for what :func:`spectrum_requests` refuses.  ``reuse=True``: as for :meth:`topk`.
+        Not differentiable."""
+        flags, several, select = spectrum_requests(self.tree, flips, paulis)
+        if reuse and arrays:
+            raise ValueError("reuse=True reads the result of the call before: give no arrays.")
+        shape = tuple(int(d) for d in self.tree.gathered_shape())
+        with self._lock:
+            st, strip = self._reduce_state(arrays, strip_exponent, check_zero, reuse)
+            ex = st["exec"]
+            if select is None and "result" in st:
+                import torch
+
+                values = torch.empty(shape, dtype=torch.float64, device=st["result"].device)
+                ex.pauli_spectrum(shape, flags, dev_out=values.data_ptr())
+            else:
+                values = ex.pauli_spectrum(shape, flags, select=select)
+            norm = ex.sample_info()[0]   # (of the statistics passes the call just ran)
+            exponent = ex.get_exponent()[0] if strip else 0.0
+        return SpectrumResult(values=values if several else np.float64(values[0]), norm=norm, exponent=exponent)
 
     # ---- a Pauli sum applied to the result, energies and their gradients (DESIGN 17) ------------------- #
 

@@ -271,6 +271,16 @@ class ContractExpression:
         self._after_reduce()
         return out
 
+    def pauli_spectrum(self, *arrays, flips=(), paulis=None, **kwargs):
+        """``expr(*arrays)`` followed by the values of ALL Pauli strings with X / Y exactly on the output indices
+        ``flips`` (or of the requested ``paulis`` among them) by one transform on the device
+        (``HipContractor.pauli_spectrum``); the expression's own ``strip_exponent`` / ``check_zero`` unless given."""
+        kwargs.setdefault("strip_exponent", self.fn.strip_exponent)
+        kwargs.setdefault("check_zero", self.fn.check_zero)
+        out = self.fn.pauli_spectrum(*arrays, flips=flips, paulis=paulis, **kwargs)
+        self._after_reduce()
+        return out
+
     def energy(self, *arrays, paulis, coeffs=None, wrt=None, normalize=False):
         """``expr(*arrays)`` followed by the energy ``sum over s of coeffs[s] <x| P_s |x>`` of the result and its
         gradient by the arrays ``wrt`` (default: all) on the device (``HipContractor.energy``, DESIGN.md section 17);

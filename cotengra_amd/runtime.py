@@ -62,6 +62,8 @@ SYMBOLS = (
     "ctg_exec_result_pauli",
     "ctg_exec_result_pauli_apply",
     "ctg_exec_result_op_apply",
+    "ctg_exec_result_pauli_spectrum",
+    "ctg_pauli_spectrum_plan",
     "ctg_exec_download_result",
     "ctg_exec_download_arena",
     "ctg_exec_get_state",
@@ -188,6 +190,9 @@ def load():
         "ctg_exec_result_pauli_apply": [vp, C.c_int64, i64p, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_double), vp, vp],
         "ctg_exec_result_op_apply": [vp, C.c_int64, i64p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                      C.POINTER(C.c_double), vp, vp],
+        "ctg_exec_result_pauli_spectrum": [vp, C.c_int64, i64p, C.POINTER(C.c_uint8), C.c_int64, i64p,
+                                           C.POINTER(C.c_double), vp],
+        "ctg_pauli_spectrum_plan": [C.c_int32, C.c_int64, i64p, C.POINTER(C.c_uint8), i64p],
         "ctg_exec_download_result": [vp, vp],
         "ctg_exec_download_arena": [vp, C.c_int64, C.c_int64, vp],
         "ctg_exec_get_state": [vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_int)],
@@ -473,6 +478,49 @@ def pauli_variant(dtype, extents, ops):
     if arr.shape[0] == 0 or (np.dtype(dtype).kind != "c" and bool(odd.all())):
         return "none"
     return f"pauli_chunk_kernel<{t}>" if _pauli_fast(ext, n) else f"pauli_general_kernel<{t}>"
+
+
+PauliSpectrumPlan = collections.namedtuple(
+    "PauliSpectrumPlan", "bits xm partner tile_bits passes pass_bits tiles scratch_bytes kernels")
+PauliSpectrumPlan.__doc__ = """The words of ``ctg_pauli_spectrum_plan`` (include/ctg_hip.h): ``bits`` = L; ``xm`` the
+flat-index mask of the flipped axes; ``partner`` 0 the element itself (``xm = 0``), 1 the thread's own 16-byte group, 2
+another group of the chunk, 3 another chunk; ``tile_bits`` = min(L, 12); ``passes`` strided passes with ``pass_bits``
+each; ``tiles`` workgroups of every launch; ``scratch_bytes`` of the vector when ``dev_out`` is not given; ``kernels``
+the launches in order as the binding spells them, ``"spectrum_tile_kernel<T>"`` then ``"spectrum_pass_kernel"`` per
+strided pass (``"spectrum_gather_kernel"`` follows when entries are selected)."""
+
+PAULI_SPECTRUM_PLAN_WORDS = 12          # CTG_PAULI_SPECTRUM_PLAN_WORDS
+PAULI_SPECTRUM_MAX_SELECT = 1 << 24     # CTG_PAULI_SPECTRUM_MAX_SELECT
+
+
+def _spectrum_args(extents, flips):
+    """``(extents int64, flips uint8)`` of a spectrum request, both with room for one entry at rank 0 -- host only:
+    ``ValueError`` for another number of flips than extents and for a flip that is no integer in 0 .. 255 (what the
+    codes mean is the library's to refuse)."""
+    ext = np.zeros(max(len(extents), 1), dtype=np.int64)
+    ext[:len(extents)] = [int(v) for v in extents]
+    raw = np.asarray(flips).reshape(-1)
+    if raw.size != len(extents):
+        raise ValueError(f"pauli_spectrum: {len(extents)} extents and {raw.size} flips.")
+    if raw.size and (raw.dtype.kind not in "iub" or raw.min() < 0 or raw.max() > 255):
+        raise ValueError("pauli_spectrum: a flip is no integer code; 0 or 1 per axis is expected.")
+    fl = np.zeros(max(len(extents), 1), dtype=np.uint8)
+    fl[:raw.size] = raw
+    return ext, fl
+
+
+def pauli_spectrum_plan(dtype, extents, flips):
+    """What ``ctg_exec_result_pauli_spectrum`` launches for a result of ``dtype`` and shape ``extents`` (every extent 1
+    or 2) with the axes ``flips`` carrying X or Y, as a :class:`PauliSpectrumPlan` (``ctg_pauli_spectrum_plan``: host
+    only, no device).  ``ValueError`` for what the call refuses of the shape and the flips."""
+    name = np.dtype(dtype).name
+    ext, fl = _spectrum_args(extents, flips)
+    words = np.zeros(PAULI_SPECTRUM_PLAN_WORDS, dtype=np.int64)
+    _check(load().ctg_pauli_spectrum_plan(_DTYPE_CODE[name], len(extents), _i64p(ext), fl.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                          _i64p(words)))
+    w = words.tolist()
+    kernels = (f"spectrum_tile_kernel<{_DTYPE_TAG[name]}>",) + ("spectrum_pass_kernel",) * w[4]
+    return PauliSpectrumPlan(w[0], w[1], w[2], w[3], w[4], tuple(w[5:5 + w[4]]), w[9], w[10], kernels)
 
 
 def pauli_apply_coeffs(coeffs, m):
@@ -984,6 +1032,42 @@ class Executor:
     def pauli_variant(self, extents, ops):
         """The name of the kernel ``pauli_result(extents, ops)`` runs on this executor (:func:`pauli_variant`)."""
         return pauli_variant(self.plan.dtype, extents, ops)
+
+    # -- all Pauli strings of one X / Y pattern by a Walsh-Hadamard transform (csrc/ctg_pauli_spectrum.hip) -- #
+
+    PAULI_SPECTRUM_MAX_SELECT = PAULI_SPECTRUM_MAX_SELECT
+
+    def pauli_spectrum(self, extents, flips, select=None, dev_out=None):
+        """``S[z] = <x| P(xm, z) |x>`` of the result tensor for ALL ``z`` in ``[0, n)`` at once
+        (``ctg_exec_result_pauli_spectrum``): ``extents`` is the shape of the result, every extent 1 or 2; ``flips`` 0
+        or 1 per axis marks the axes that carry X or Y, ``xm`` is the mask of their flat-index bits.  ``P(xm, z)`` has Y
+        on the bits of ``xm & z``, X on ``xm & ~z``, Z on ``z & ~xm``; its value is what :meth:`pauli_result` gives
+        that string, NOT normalised, in other bits.  Without ``select``: a float64 array of shape ``extents`` (Z / Y on
+        the axes where the coordinate is 1), or ``None`` when ``dev_out`` -- a device address of ``n`` doubles that
+        does not overlap the result tensor -- takes it instead.  With ``select``, up to ``PAULI_SPECTRUM_MAX_SELECT``
+        flat indices: ``S[select]`` as a float64 array, and ``dev_out``, if given, still receives all of ``S``.  The
+        bits of an entry depend on (dtype, extents, flips, the tensor's bytes) alone.  ``ValueError`` for what the
+        call refuses (nothing is launched) and for a result whose ``sum p`` is not finite."""
+        ext, fl = _spectrum_args(extents, flips)
+        sel = None
+        if select is not None:
+            raw = np.asarray(select)
+            if raw.size and raw.dtype.kind not in "iu":
+                raise ValueError(f"pauli_spectrum: select of dtype {raw.dtype}; flat indices are integers.")
+            sel = np.ascontiguousarray(raw, dtype=np.int64).reshape(-1)
+            out = np.zeros(sel.size, dtype=np.float64)
+        else:
+            out = None if dev_out else np.zeros(tuple(int(v) for v in extents), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        _check(load().ctg_exec_result_pauli_spectrum(
+            self.handle, len(extents), _i64p(ext), fl.ctypes.data_as(C.POINTER(C.c_uint8)), 0 if sel is None else sel.size,
+            None if sel is None else _i64p(sel), None if out is None else out.ctypes.data_as(dp),
+            C.c_void_p(int(dev_out) if dev_out else None)))
+        return out
+
+    def pauli_spectrum_plan(self, extents, flips):
+        """What ``pauli_spectrum(extents, flips)`` launches on this executor (:func:`pauli_spectrum_plan`)."""
+        return pauli_spectrum_plan(self.plan.dtype, extents, flips)
 
     # -- a Pauli sum applied to the result tensor (csrc/ctg_pauli_apply.hip) -- #
 

@@ -1110,6 +1110,15 @@ class ContractionTree:
 
         return _tree_contractor(self, order).rdm_wide(*arrays, keep=keep, **kwargs)
 
+    def contract_pauli_spectrum(self, arrays, flips=(), paulis=None, order=None, **kwargs):
+        """:meth:`contract` followed by ``<x| P |x>`` for ALL Pauli strings with X / Y exactly on the output indices
+        ``flips`` -- or, with ``paulis``, for those of them that are requested -- by one Walsh-Hadamard transform on
+        the device (``HipContractor.pauli_spectrum``; ``kwargs``: ``strip_exponent``, ``check_zero``, ``reuse``).
+        Returns a ``SpectrumResult``."""
+        from .contractor import _tree_contractor
+
+        return _tree_contractor(self, order).pauli_spectrum(*arrays, flips=flips, paulis=paulis, **kwargs)
+
     def contract_expectation(self, arrays, paulis, order=None, **kwargs):
         """:meth:`contract` followed by the expectation values ``<x| P |x>`` of the Pauli strings ``paulis`` over
         the output indices (a string over ``IXYZ``, a mapping ``{label: letter}``, a sequence of ``(label, letter)``

@@ -719,6 +719,60 @@ int ctg_exec_result_op_apply(ctg_exec* exec, int64_t rank, const int64_t* extent
 int ctg_exec_result_rdm_wide(ctg_exec* exec, int64_t rank, const int64_t* extents, const int32_t* keep, void* out,
                              double* purity);
 int ctg_rdm_wide_plan(int32_t dtype, int64_t rank, const int64_t* extents, const int32_t* keep, int64_t* words);
+/* Added to ABI 10 WITHOUT a bump of CTG_ABI_VERSION likewise (two new symbols; a binding that needs them looks them up):
+ * the expectation values of ALL 2^L Pauli strings that share one X / Y pattern, by one Walsh-Hadamard transform on the
+ * device (csrc/ctg_pauli_spectrum.hip) -- every <Z_i Z_j> and higher correlator, the Walsh
+ * spectrum of an output distribution, all 4^k strings of a support (one call per X pattern).  extents[rank] is the shape
+ * of the result x, n = 2^L elements: every extent must be 1 or 2.  flips[rank] in {0, 1} marks the axes that carry X or
+ * Y (extent 2); xm is the mask of their flat-index bits (the flat bit of an axis is log2 of its row-major stride).  For
+ * z in [0, n) the string P(xm, z) has Y on the bits of xm & z, X on xm & ~z, Z on z & ~xm, I elsewhere, and ny(z) =
+ * popcount(xm & z) letters Y.  The spectrum is
+ *   S[z] = <x| P(xm, z) |x>,
+ * the value ctg_exec_result_pauli gives that string: NOT normalised, S[0] = sum p for xm = 0; row-major over the
+ * tensor's own axes, Z / Y on the axes where the coordinate is 1.  With select == NULL the n doubles go to out (host, may
+ * be NULL) and / or dev_out (device, 8-byte aligned, may be NULL; it must not overlap the result tensor); m is not read.
+ * With select[m], m <= CTG_PAULI_SPECTRUM_MAX_SELECT entries in [0, n), out[s] = S[select[s]] (out must be given) and
+ * dev_out, if given, still receives the whole spectrum.  The tensor is read as the calls above read it (whoever owns
+ * the memory, the mantissa under strip_exponent, after the stream's earlier work, after the statistics passes, which
+ * run first) and never written; the stream is synchronised.  CTG_E_NORM when sum p is not finite; an all-zero tensor
+ * gives zeros.  CTG_E_INVALID -- checked on the host before anything is reserved or launched, all buffers untouched --
+ * for everything ctg_exec_result_pauli refuses about exec, rank and extents, a null flips, an extent above 2, a flip
+ * code above 1 or on an axis of extent 1, neither out nor dev_out, select without out, m out of range, a select entry
+ * outside [0, n), a dev_out that is misaligned or overlaps the result tensor.  CTG_E_NOMEM when the scratch cannot be
+ * reserved.
+ *   - Arithmetic, all fp64, nothing contracted, associated as written: with p = x[j ^ xm], w = x[j],
+ *       u[j] = (p.re w.re + p.im w.im) + (p.re w.im - p.im w.re)     (real plans: u[j] = p w),
+ *     then for the bits b = 0, 1, .., L - 1 IN THIS ORDER every pair (a, c) = (v[j], v[j | 2^b]) becomes (a + c, a - c),
+ *     then S[z] = (-1)^ceil(ny(z) / 2) v[z] by a flip of the sign bit; real plans: S[z] = +0.0 for odd ny(z).  (Re
+ *     conj(p) w is symmetric under j <-> j ^ xm, Im conj(p) w antisymmetric: the part that does not belong to the parity
+ *     of ny(z) cancels to rounding noise, so one real transform serves both parities.)
+ *   - The bits of S are a function of (dtype, extents, flips, the tensor's bytes) alone: not of select, of which output
+ *     was asked, earlier calls in the same scratch, or the executor.  No atomics.
+ *   - |S[z] - exact| <= 2 (8 n + 1) 2^-53 sqrt(2) sum p for complex plans, 2 (n + 1) 2^-53 sum p for real plans.
+ * ctg_pauli_spectrum_plan (host only, touches no device) returns what the call launches for a result of `dtype`
+ * (CTG_F32 .. CTG_C128) whose extents' product stands for result_elems, the same refusals included:
+ *   words[0] L
+ *   words[1] xm
+ *   words[2] partner      where x[j ^ xm] comes from -- 0: xm = 0, the element itself; 1: the thread's own 16-byte group;
+ *                         2: another group of the same chunk of 4096 elements; 3: the chunk c ^ (xm >> 12).  Always a
+ *                         second 16-byte load inside the tile pass: no separate form kernel runs.
+ *   words[3] tile bits    min(L, 12): the bits "spectrum_tile_kernel<T>", T in float | double | c64 | c128, transforms
+ *   words[4] passes       launches of "spectrum_pass_kernel": 0 for L <= 12, 1 for 13 .. 20, 2 for 21 .. 28, ...
+ *   words[5 .. 8]         the bits of each pass, at most 8, ascending from bit 12
+ *   words[9] tiles        workgroups of every launch: max(1, n / 4096)
+ *   words[10] scratch     bytes of the vector in the executor's scratch when dev_out is not given (8 n, to 256); a
+ *                         select table adds 8 m (to 256) twice: its copy and its values ("spectrum_gather_kernel")
+ *   words[11] name        the dtype code: T of the tile kernel
+ * Tile pass: 256 threads, two workgroups per CU, a workgroup per chunk of 4096 consecutive elements; u goes to 32 KiB of
+ * LDS, the bits are transformed four at a time with 16 values per thread in registers.  Strided pass: in place, a
+ * workgroup holds 2^bits rows of 4096 / 2^bits >= 16 consecutive doubles (runs of 128 bytes at least).  The last pass
+ * applies the sign and the zeros.  Scratch: the buffer of ctg_exec_result_topk (counted by ctg_exec_device_bytes, freed
+ * by ctg_exec_destroy).  Not differentiable; no multi-rank entry, as above. */
+#define CTG_PAULI_SPECTRUM_MAX_SELECT (1 << 24)
+#define CTG_PAULI_SPECTRUM_PLAN_WORDS 12
+int ctg_exec_result_pauli_spectrum(ctg_exec* exec, int64_t rank, const int64_t* extents, const uint8_t* flips, int64_t m,
+                                   const int64_t* select, double* out, void* dev_out);
+int ctg_pauli_spectrum_plan(int32_t dtype, int64_t rank, const int64_t* extents, const uint8_t* flips, int64_t* words);
 /* debugging aid: copy `n` elements of the arena starting at element `offset`
  * to the host (synchronous) */
 int ctg_exec_download_arena(ctg_exec* exec, int64_t offset, int64_t n, void* host_out);

@@ -13,7 +13,8 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ["ctg_sample.hip", "ctg_reduce.hip", "ctg_rdm.hip", "ctg_rdm_wide.hip", "ctg_pauli.hip", "ctg_pauli_apply.hip", "ctg_op_apply.hip"]
+SOURCES = ["ctg_sample.hip", "ctg_reduce.hip", "ctg_rdm.hip", "ctg_rdm_wide.hip", "ctg_pauli.hip", "ctg_pauli_apply.hip", "ctg_op_apply.hip",
+           "ctg_pauli_spectrum.hip"]
 FIELDS = [("VGPRs", "vgpr"), ("AGPRs", "agpr"), ("TotalSGPRs", "sgpr"), ("ScratchSize [bytes/lane]", "scratch"),
           ("LDS Size [bytes/block]", "lds"), ("Occupancy [waves/SIMD]", "occ")]
 
