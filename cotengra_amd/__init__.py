@@ -22,6 +22,7 @@ from .contractor import ExpectationResult, HipContractor, MarginalResult, RdmRes
 from .contractor import ApplyResult, EnergyResult  # noqa: F401,E402
 from .contractor import operator_requests, pauli_requests  # noqa: F401,E402
 from .contractor import SpectrumResult, spectrum_requests  # noqa: F401,E402
+from .contractor import CostResult, cost_requests  # noqa: F401,E402
 from .interface import (  # noqa: F401,E402
     array_contract,
     array_contract_expression,

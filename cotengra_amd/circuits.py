@@ -648,6 +648,67 @@ def z_correlations(n, gates, qubits=None, fixed=None, optimize="greedy", dtype="
     return z, zz, zz - np.outer(z, z), res.norm
 
 
+def maxcut_terms(edges, weights=None):
+    """The Z-type terms of the MaxCut cost ``sum over edges (i, j) of w_ij (1 - Z_i Z_j) / 2`` -- the weight of the cut a
+    bitstring makes -- as ``(terms, coeffs)`` for :func:`cost_statistics`: per edge the dict ``{i: "Z", j: "Z"}`` with
+    coefficient ``-w_ij / 2``, and the constant ``sum w_ij / 2`` as the identity string ``{}`` in front.  ``weights``:
+    one real per edge (default: ones).  ``ValueError`` for an edge that is no pair of two different non-negative
+    qubits and for ``weights`` of another length or not finite."""
+    pairs = []
+    for e in edges:
+        if len(e) != 2 or int(e[0]) == int(e[1]) or int(e[0]) < 0 or int(e[1]) < 0:
+            raise ValueError(f"maxcut_terms: the edge {e!r} is no pair of two different qubits.")
+        pairs.append((int(e[0]), int(e[1])))
+    w = np.ones(len(pairs), dtype=np.float64) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.size != len(pairs):
+        raise ValueError(f"maxcut_terms: {w.size} weights for {len(pairs)} edges.")
+    if not np.all(np.isfinite(w)):
+        raise ValueError("maxcut_terms: a weight is not finite.")
+    terms = [{}] + [{i: "Z", j: "Z"} for i, j in pairs]
+    return terms, np.concatenate([[0.5 * float(np.sum(w))], -0.5 * w])
+
+
+def cost_statistics(n, gates, terms, coeffs=None, qubits=None, fixed=None, levels=(), tail="lower", edges=None, optimize="greedy",
+                    dtype="complex64", target_size=None):
+    """The distribution of the classical cost ``C = sum_k coeffs[k] Z-string_k`` in the output state of the ``n``-qubit
+    circuit ``gates``: mean, variance, ``CVaR_alpha`` and quantiles at ``levels``, a histogram over ``edges``, the
+    optimum over all bitstrings of the open qubits and the probability of sampling it -- the QAOA objectives, taken on
+    the device from one contraction (``ContractionTree.contract_cost``).  ``terms``: requests as
+    for :func:`pauli_expectation` with letters I and Z only (a dict ``{qubit: "Z"}``, ``{}`` for a constant; or a
+    string of ``n`` letters); :func:`maxcut_terms` builds them for a graph.  ``qubits`` (default: every qubit not in
+    ``fixed``): the qubits a term may name; ``fixed``: a dict ``{qubit: 0 | 1}`` as for :func:`pauli_expectation`.
+    Returns the ``CostResult``; its ``argmin`` / ``argmax`` are bit tuples over the open qubits in qubit order.
+    ``ValueError`` -- before any device work -- for what :func:`pauli_expectation` refuses of the requests, a letter X
+    or Y, a term on a qubit outside ``qubits``; and for a state of norm zero."""
+    from .interface import array_contract_tree
+
+    n, fixed, several, letters, coeffs = _circuit_pauli_requests("cost_statistics", n, terms, fixed, coeffs)
+    open_qubits = [q for q in range(n) if q not in fixed]
+    qs = set(open_qubits if qubits is None else (int(q) for q in qubits))
+    for q in qs:
+        if q < 0 or q >= n or q in fixed:
+            raise ValueError(f"cost_statistics: qubit {q} is outside the circuit or fixed.")
+    for row in letters:
+        for q, c in row.items():
+            if c not in "IZ":
+                raise ValueError(f"cost_statistics: the letter {c!r} on qubit {q}; a classical cost has I and Z only.")
+            if c == "Z" and q not in qs:
+                raise ValueError(f"cost_statistics: a term names qubit {q}, which is not among qubits = {sorted(qs)}.")
+    template = "".join(str(fixed[q]) if q in fixed else "?" for q in range(n))
+    inputs, output, size_dict, arrays = circuit_to_network(n, gates, template, simplify=True, dtype=dtype)
+    tree = array_contract_tree(inputs, output, size_dict, optimize=optimize)
+    if [tuple(t) for t in tree.inputs] != [tuple(t) for t in inputs] or tuple(tree.output) != tuple(output):
+        raise ValueError("optimize: the tree is not over this circuit's network.")
+    if target_size is not None:
+        tree = tree.slice(target_size=target_size)
+    label = dict(zip(open_qubits, output))   # (one output index per open qubit, in qubit order)
+    reqs = [{label[q]: c for q, c in row.items() if c == "Z"} for row in letters]
+    res = tree.contract_cost(arrays, terms=reqs, coeffs=coeffs, levels=levels, tail=tail, edges=edges)
+    if not res.norm > 0:
+        raise ValueError("cost_statistics: the state has norm zero.")
+    return res
+
+
 def gate_derivatives(name, params=()):
     """``[dU / d params[0], ...]`` of :func:`gate_matrix`, analytic: one matrix for ``rz``, two for ``fs``, none for a
     gate without parameters."""

@@ -582,6 +582,44 @@ class SpectrumResult(collections.namedtuple("SpectrumResult", "values norm expon
     __slots__ = ()
 
 
+class CostResult(collections.namedtuple(
+        "CostResult", "mean variance minimum maximum argmin argmax support_min support_max p_min p_max thresholds cvar hist "
+                      "values norm exponent raw")):
+    """What ``HipContractor.cost`` returns for a classical cost ``C(z)`` under ``p(z) = |x_z|^2 / norm`` (DESIGN.md section
+    22): ``mean`` and ``variance`` of ``C``; ``minimum`` / ``maximum`` of ``C`` over ALL bitstrings with ``argmin`` /
+    ``argmax`` their coordinates in ``tree.gathered_shape()`` (the lowest flat index among ties); ``support_min`` /
+    ``support_max`` the extremes over the bitstrings of non-zero weight and ``p_min`` / ``p_max`` the probability of
+    sampling a bitstring of that cost; per level ``thresholds`` (the quantile ``t_l``) and ``cvar`` (float64 arrays in
+    the order of ``levels``); ``hist`` the probability per bin ``edges[b] <= C < edges[b + 1]`` (``None`` without
+    edges; the outer masses are in ``raw``); ``values`` the cost vector in ``tree.gathered_shape()`` with
+    ``keep_values`` (a tensor on the device for ROCm torch inputs), else ``None``; ``norm`` = ``sum |x|^2``; the base-10
+    ``exponent`` taken out under ``strip_exponent``.  ``raw``: a dict of the integers every mass comes from -- ``s``,
+    ``W``, per level ``A``, ``below``, ``at`` and the fp64 ``tail``, ``argmin_flat`` / ``argmax_flat`` /
+    ``support_argmin`` / ``support_argmax`` (flat indices; -1 without support), ``mass_min`` / ``mass_max``, ``hist``
+    (``len(edges) + 1`` integers: below the first edge, the bins, at or above the last), ``sum_pc`` / ``sum_pcc``; a
+    mass is its integer times ``2^-s``.  An all-zero result (``W = 0``): ``mean``, ``variance``, every probability,
+    threshold and ``cvar`` are 0.0, ``support_min`` / ``support_max`` 0.0."""
+
+    __slots__ = ()
+
+
+def cost_requests(tree, terms, coeffs=None):
+    """``terms`` and ``coeffs`` of ``HipContractor.cost`` as ``(ops, coeffs)`` -- host only: ``ops`` the uint8 ``(m,
+    len(tree.output))`` array of codes 0 = I and 3 = Z of :func:`pauli_requests` (one request or a list of requests,
+    up to ``Executor.COST_MAX_TERMS``), ``coeffs`` the float64 ``(m,)`` array (``None``: ones).  ``ValueError`` for what
+    :func:`pauli_requests` refuses, a letter X or Y (no classical cost), an output index of extent above 2, ``coeffs``
+    of another length and a coefficient that is not finite."""
+    output = list(tree.output)
+    for ix, d in zip(output, tree.gathered_shape()):
+        if int(d) > 2:
+            raise ValueError(f"cost: output index {ix!r} has extent {int(d)}; with terms every extent must be 1 or 2.")
+    several, ops = pauli_requests(tree, terms, max_requests=runtime.Executor.COST_MAX_TERMS)
+    if ((ops == 1) | (ops == 2)).any():
+        r = int(np.flatnonzero(((ops == 1) | (ops == 2)).any(axis=1))[0])
+        raise ValueError(f"cost: term {r} carries X or Y; a classical cost has I and Z only.")
+    return ops, runtime.pauli_apply_coeffs(coeffs, len(ops))
+
+
 def spectrum_requests(tree, flips, paulis=None):
     """``flips`` and ``paulis`` of ``HipContractor.pauli_spectrum`` as ``(flags, several?, select)`` -- host only:
     ``flags`` 0 / 1 per output index of ``tree.gathered_shape()``, ``select`` the flat indices of the requested
@@ -617,6 +655,39 @@ def spectrum_requests(tree, flips, paulis=None):
         stride[a] = stride[a + 1] * shape[a + 1]
     select = (((ops == 2) | (ops == 3)).astype(np.int64) * stride[None, :]).sum(axis=1) if len(shape) else np.zeros(len(ops), np.int64)
     return flags, several, np.ascontiguousarray(select, dtype=np.int64)
+
+
+def _cost_result(words, hist, nl, shape, values, exponent):
+    """The :class:`CostResult` of the words and integer masses of ``Executor.cost_result``."""
+    f = words.view(np.float64)
+    s, W, norm = int(words[0]), int(words[1]), float(f[16])
+    unit = 2.0 ** -s
+
+    def coords(flat):
+        return tuple(int(c) for c in np.unravel_index(flat, shape)) if shape and flat >= 0 else ()
+
+    w0, wn = runtime.COST_LEVEL_WORD0, runtime.COST_LEVEL_WORDS
+    A = [int(words[w0 + wn * l]) for l in range(nl)]
+    t = np.array([f[w0 + wn * l + 1] for l in range(nl)], dtype=np.float64)
+    below = [int(words[w0 + wn * l + 2]) for l in range(nl)]
+    at = [int(words[w0 + wn * l + 3]) for l in range(nl)]
+    tails = np.array([f[w0 + wn * l + 4] for l in range(nl)], dtype=np.float64)
+    cvar = np.zeros(nl, dtype=np.float64)
+    for l in range(nl):
+        if A[l] > 0:
+            cvar[l] = (tails[l] + ((A[l] - below[l]) * unit) * t[l]) / (A[l] * unit)
+    live = W > 0 and norm > 0
+    mean = float(f[2]) / norm if live else 0.0
+    var = float(f[3]) / norm - mean * mean if live else 0.0
+    raw = dict(s=s, W=W, A=A, below=below, at=at, tail=tails, argmin_flat=int(words[5]), argmax_flat=int(words[7]),
+               support_argmin=int(words[9]), support_argmax=int(words[12]), mass_min=int(words[10]), mass_max=int(words[13]),
+               hist=None if hist is None else hist.copy(), sum_pc=float(f[2]), sum_pcc=float(f[3]))
+    prob = (lambda m: m * unit / norm) if live else (lambda m: 0.0)
+    return CostResult(
+        mean=mean, variance=var, minimum=float(f[4]), maximum=float(f[6]), argmin=coords(int(words[5])), argmax=coords(int(words[7])),
+        support_min=float(f[8]), support_max=float(f[11]), p_min=prob(int(words[10])), p_max=prob(int(words[13])),
+        thresholds=t, cvar=cvar, hist=None if hist is None else np.array([prob(int(m)) for m in hist[1:-1]], dtype=np.float64),
+        values=values, norm=norm, exponent=exponent, raw=raw)
 
 
 class HipContractor:
@@ -1402,6 +1473,83 @@ class HipContractor:
             norm = ex.sample_info()[0]   # (of the statistics passes the call just ran)
             exponent = ex.get_exponent()[0] if strip else 0.0
         return SpectrumResult(values=values if several else np.float64(values[0]), norm=norm, exponent=exponent)
+
+    # ---- the distribution of a classical cost over the result ------------------------------- #
+
+    def cost(self, *arrays, terms=None, coeffs=None, values=None, levels=(), edges=None, tail="lower", keep_values=False,
+             strip_exponent=False, check_zero=False, reuse=False):
+        """Contract (all slices, as a call does) and return the statistics of a classical cost ``C(z)`` under the
+        output distribution ``p(z) = |x_z|^2 / norm`` -- mean, variance, ``CVaR_alpha`` and quantiles at ``levels``, a
+        histogram over ``edges``, the optimum of ``C`` over all bitstrings and the probability of sampling it -- on the
+        device; neither the tensor nor the cost vector crosses the bus (``ctg_exec_result_cost``).
+        The cost is either ``terms`` with real ``coeffs`` (default: ones): Z-type requests as for :meth:`expectation`,
+        ``C(z) = sum_s coeffs[s] (-1)^popcount(z & m_s)``, every output index of extent 1 or 2; or ``values``: an
+        array of ``tree.gathered_shape()`` real numbers (numpy, or a ROCm torch tensor), any extents.  ``levels``: up
+        to 8 numbers in (0, 1]; ``tail``: ``"lower"`` (minimisation: the best ``alpha`` mass is the lowest costs) or
+        ``"upper"``; ``edges``: 2 .. 4097 ascending finite bin edges.  Every probability is a sum of integer weights
+        ``rint(p 2^s)`` (exact, order-free); ``keep_values=True`` also returns the cost vector.  Returns a
+        :class:`CostResult`.  ``ValueError`` -- before the device is touched -- for what :func:`cost_requests` refuses,
+        both or neither source, ``values`` of another shape, complex or not finite (a device tensor's entries are checked
+        on the device), a level outside (0, 1], more than 8 levels, edges that are not ascending and finite and a
+        ``tail`` that is neither ``"lower"`` nor ``"upper"``.  ``reuse=True``: as for :meth:`topk`.  Not differentiable."""
+        shape = tuple(int(d) for d in self.tree.gathered_shape())
+        if (terms is None) == (values is None):
+            raise ValueError("cost: give exactly one of terms and values.")
+        if tail not in ("lower", "upper"):
+            raise ValueError(f"cost: tail = {tail!r} is neither 'lower' nor 'upper'.")
+        ops = co = None
+        if terms is not None:
+            ops, co = cost_requests(self.tree, terms, coeffs)
+        else:
+            if coeffs is not None:
+                raise ValueError("cost: coeffs belong to terms, not to values.")
+            if not _is_torch(values):
+                values = np.asarray(values)
+            if tuple(values.shape) != shape:
+                raise ValueError(f"cost: values of shape {tuple(values.shape)}; the result has {shape}.")
+            if not _is_torch(values):
+                if values.dtype.kind not in "iufb":
+                    raise ValueError(f"cost: values of dtype {values.dtype}; real numbers are expected.")
+                values = np.ascontiguousarray(values, dtype=np.float64)
+                if not np.all(np.isfinite(values)):
+                    raise ValueError("cost: a value is not finite.")
+            elif values.is_complex():
+                raise ValueError(f"cost: values of dtype {values.dtype}; real numbers are expected.")
+        lev = np.asarray(levels, dtype=np.float64).reshape(-1)
+        if lev.size > runtime.Executor.COST_MAX_LEVELS:
+            raise ValueError(f"cost: {lev.size} levels; at most {runtime.Executor.COST_MAX_LEVELS} are taken by one call.")
+        if not np.all((lev > 0.0) & (lev <= 1.0)):
+            raise ValueError(f"cost: the levels {lev.tolist()} are not all in (0, 1].")
+        ed = None
+        if edges is not None:
+            ed = np.asarray(edges, dtype=np.float64).reshape(-1)
+            if ed.size < 2 or ed.size > runtime.Executor.COST_MAX_EDGES:
+                raise ValueError(f"cost: {ed.size} edges; between 2 and {runtime.Executor.COST_MAX_EDGES} are taken.")
+            if not np.all(np.isfinite(ed)) or not np.all(ed[1:] > ed[:-1]):
+                raise ValueError("cost: the edges are not finite and strictly ascending.")
+        if reuse and arrays:
+            raise ValueError("reuse=True reads the result of the call before: give no arrays.")
+        with self._lock:
+            st, strip = self._reduce_state(arrays, strip_exponent, check_zero, reuse)
+            ex = st["exec"]
+            dev_vals = out_vals = None
+            if values is not None or keep_values:
+                import torch
+
+                dev = st["result"].device if "result" in st else torch.device("cuda", ex.device)
+                if values is not None:
+                    dev_vals = torch.as_tensor(values).to(device=dev, dtype=torch.float64).contiguous()
+                if keep_values:
+                    out_vals = torch.empty(shape, dtype=torch.float64, device=dev)
+                torch.cuda.current_stream(dev).synchronize()
+            words, hist = ex.cost_result(
+                shape, ops=ops, coeffs=co, dev_cost=None if dev_vals is None else dev_vals.data_ptr(),
+                tail=-1 if tail == "lower" else 1, levels=lev, edges=ed,
+                dev_cost_out=None if out_vals is None else out_vals.data_ptr())
+            exponent = ex.get_exponent()[0] if strip else 0.0
+        if out_vals is not None and "result" not in st:
+            out_vals = out_vals.cpu().numpy()
+        return _cost_result(words, hist, lev.size, shape, out_vals, exponent)
 
     # ---- a Pauli sum applied to the result, energies and their gradients (DESIGN 17) ------------------- #
 

@@ -27,7 +27,7 @@
 //   spectrum_pass_kernel      a strided pass over the bits s .. s + nb - 1 of the vector, s >= 12, nb <= 8, in place: a
 //                             workgroup holds 2^nb rows (stride 2^s) of 4096 / 2^nb >= 16 consecutive doubles -- runs
 //                             of 128 bytes at least.  L <= 12: no such pass; 13 .. 20: one; 21 .. 28: two; ...
-//   wht_local                 what both share: the butterflies of the local bits b0 .. b1 - 1 of 4096 doubles in LDS in
+//   wht_local (ctg_wht.h)     what both share, and the kernels of ctg_cost.hip with them: the butterflies of the local bits b0 .. b1 - 1 of 4096 doubles in LDS in
 //                             rounds of four bits; in a round a thread holds the 16 values that differ in those four
 //                             bits.  Slot i of the LDS image is i ^ ((i >> 5) & 31): the three rounds' 8-byte reads are
 //                             then conflict-free or 2-way (linear: 16-way in the first round).
@@ -42,11 +42,9 @@
 
 #include "ctg_result_elem.h"
 #include "ctg_result_host.h"
+#include "ctg_wht.h"
 
 namespace ctg {
-
-constexpr int kSpecPassBits = 8;     // bits of a strided pass, at most
-constexpr int kSpecMaxPasses = 4;    // 12 + 4 * 8 >= 40 = log2(kReduceMaxElems)
 
 // u of one element: every product and sum rounded once, never fused
 template <typename T> struct SpecElem;
@@ -81,38 +79,6 @@ template <> struct SpecElem<double2> {
         return re + im;
     }
 };
-
-// where local index i of a tile lives in its LDS image
-__device__ __forceinline__ int spec_slot(int i) { return i ^ ((i >> 5) & 31); }
-
-// The butterflies of the local bits b0 .. b1 - 1 (wave-uniform, within 0 .. 12) of the tile in ds, ascending.  Begins
-// and ends with a barrier: the caller's writes are seen, and so is the result.
-__device__ __forceinline__ void wht_local(double* ds, int tid, int b0, int b1) {
-    __syncthreads();
-#pragma unroll
-    for (int lo = 0; lo < kResultChunkBits; lo += 4) {
-        if (b1 <= lo || b0 >= lo + 4) continue;
-        // the 16 local indices that differ in the bits lo .. lo + 3: those bits are k, the others tid's
-        const int rest = ((tid >> lo) << (lo + 4)) | (tid & ((1 << lo) - 1));
-        double v[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) v[k] = ds[spec_slot(rest | (k << lo))];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (lo + j < b0 || lo + j >= b1) continue;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                if (k & (1 << j)) continue;
-                const double a = v[k], c = v[k | (1 << j)];
-                v[k] = a + c;
-                v[k | (1 << j)] = a - c;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 16; ++k) ds[spec_slot(rest | (k << lo))] = v[k];
-        __syncthreads();
-    }
-}
 
 // entry z of the spectrum from W[z]: the sign (-1)^ceil(ny / 2) as a flip of the sign bit; +0.0 for odd ny of a real plan
 __device__ __forceinline__ double spec_finish(double w, int64_t z, int64_t xm, int real) {
@@ -190,9 +156,8 @@ __global__ __launch_bounds__(kSampleThreads, 2) void spectrum_pass_kernel(double
     const int tid = threadIdx.x;
     const int cb = kResultChunkBits - nb;
     const int64_t q = blockIdx.x;
-    const int lowbits = s - cb;
-    const int64_t base = ((q & (((int64_t)1 << lowbits) - 1)) << cb) | ((q >> lowbits) << (s + nb));
-    auto where = [&](int l) { return base | ((int64_t)(l >> cb) << s) | (int64_t)(l & ((1 << cb) - 1)); };
+    const int64_t base = wht_pass_base(q, s, nb);
+    auto where = [&](int l) { return wht_pass_where(base, l, s, nb); };
 #pragma unroll
     for (int i = 0; i < kResultChunk / 2 / kSampleThreads; ++i) {
         const int l = (i * kSampleThreads + tid) * 2;   // (l and l + 1 share a row: cb >= 4)

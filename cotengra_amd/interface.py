@@ -281,6 +281,15 @@ class ContractExpression:
         self._after_reduce()
         return out
 
+    def cost(self, *arrays, terms=None, coeffs=None, values=None, **kwargs):
+        """``expr(*arrays)`` followed by the statistics of a classical cost under the output distribution on the device
+        (``HipContractor.cost``); the expression's own ``strip_exponent`` / ``check_zero`` unless given."""
+        kwargs.setdefault("strip_exponent", self.fn.strip_exponent)
+        kwargs.setdefault("check_zero", self.fn.check_zero)
+        out = self.fn.cost(*arrays, terms=terms, coeffs=coeffs, values=values, **kwargs)
+        self._after_reduce()
+        return out
+
     def energy(self, *arrays, paulis, coeffs=None, wrt=None, normalize=False):
         """``expr(*arrays)`` followed by the energy ``sum over s of coeffs[s] <x| P_s |x>`` of the result and its
         gradient by the arrays ``wrt`` (default: all) on the device (``HipContractor.energy``, DESIGN.md section 17);

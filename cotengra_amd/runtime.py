@@ -64,6 +64,8 @@ SYMBOLS = (
     "ctg_exec_result_op_apply",
     "ctg_exec_result_pauli_spectrum",
     "ctg_pauli_spectrum_plan",
+    "ctg_exec_result_cost",
+    "ctg_cost_plan",
     "ctg_exec_download_result",
     "ctg_exec_download_arena",
     "ctg_exec_get_state",
@@ -193,6 +195,9 @@ def load():
         "ctg_exec_result_pauli_spectrum": [vp, C.c_int64, i64p, C.POINTER(C.c_uint8), C.c_int64, i64p,
                                            C.POINTER(C.c_double), vp],
         "ctg_pauli_spectrum_plan": [C.c_int32, C.c_int64, i64p, C.POINTER(C.c_uint8), i64p],
+        "ctg_exec_result_cost": [vp, C.c_int64, i64p, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_double), vp, C.c_int32,
+                                 C.c_int64, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), i64p, i64p, vp],
+        "ctg_cost_plan": [C.c_int32, C.c_int64, i64p, C.c_int32, C.c_int64, C.c_int64, i64p],
         "ctg_exec_download_result": [vp, vp],
         "ctg_exec_download_arena": [vp, C.c_int64, C.c_int64, vp],
         "ctg_exec_get_state": [vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_int)],
@@ -521,6 +526,68 @@ def pauli_spectrum_plan(dtype, extents, flips):
     w = words.tolist()
     kernels = (f"spectrum_tile_kernel<{_DTYPE_TAG[name]}>",) + ("spectrum_pass_kernel",) * w[4]
     return PauliSpectrumPlan(w[0], w[1], w[2], w[3], w[4], tuple(w[5:5 + w[4]]), w[9], w[10], kernels)
+
+
+CostPlan = collections.namedtuple(
+    "CostPlan", "bits n tile_bits passes pass_bits tiles digit_passes digit_launches grid scratch_bytes chunks hist_words kernels")
+CostPlan.__doc__ = """The words of ``ctg_cost_plan`` (include/ctg_hip.h): ``bits`` = L for terms, -1 for values; ``n``
+elements; ``tile_bits`` = min(L, 12); ``passes`` strided passes with ``pass_bits`` each; ``tiles`` workgroups of a
+transform launch; ``digit_passes`` per level (6; 1 without levels) and ``digit_launches`` = 1 + 5 nl in all; ``grid``
+workgroups of a digit pass and of the final pass; ``scratch_bytes`` with the vector in the scratch and no term table;
+``chunks`` of 4096 elements; ``hist_words`` = ne + 1 (0 without edges); ``kernels`` the launches in order as the binding
+spells them."""
+
+COST_MAX_TERMS = 1 << 20     # CTG_COST_MAX_TERMS
+COST_MAX_LEVELS = 8          # CTG_COST_MAX_LEVELS
+COST_MAX_EDGES = 4097        # CTG_COST_MAX_EDGES
+COST_WORDS = 64              # CTG_COST_WORDS
+COST_LEVEL_WORD0 = 24        # CTG_COST_LEVEL_WORD0
+COST_LEVEL_WORDS = 5         # CTG_COST_LEVEL_WORDS
+COST_PLAN_WORDS = 16         # CTG_COST_PLAN_WORDS
+COST_TERMS, COST_VALUES = 0, 1
+
+
+def cost_plan(dtype, extents, source="terms", nl=0, ne=0):
+    """What ``ctg_exec_result_cost`` launches for a result of ``dtype`` and shape ``extents``, the cost from ``source``
+    (``"terms"``: every extent 1 or 2; ``"values"``: any extents), ``nl`` levels and ``ne`` edges, as a
+    :class:`CostPlan` (``ctg_cost_plan``: host only, no device).  ``ValueError`` for what the call refuses of these."""
+    name = np.dtype(dtype).name
+    if source not in ("terms", "values"):
+        raise ValueError(f"cost_plan: source = {source!r} is neither 'terms' nor 'values'.")
+    ext = np.zeros(max(len(extents), 1), dtype=np.int64)
+    ext[:len(extents)] = [int(v) for v in extents]
+    words = np.zeros(COST_PLAN_WORDS, dtype=np.int64)
+    _check(load().ctg_cost_plan(_DTYPE_CODE[name], len(extents), _i64p(ext), COST_TERMS if source == "terms" else COST_VALUES,
+                                int(nl), int(ne), _i64p(words)))
+    w = words.tolist()
+    tag = _DTYPE_TAG[name]
+    first = ("cost_scatter_kernel", "cost_tile_kernel") + ("cost_pass_kernel",) * w[3] if source == "terms" else ("cost_check_kernel",)
+    digit = (f"cost_digit_kernel<{tag}>", "cost_rowsum_kernel", "cost_select_kernel")
+    last = (f"cost_final_kernel<{tag},{1 if ne else 0}>",) + (("cost_rowsum_kernel",) if ne else ()) + ("cost_finish_kernel",)
+    kernels = first + digit[:2] + (digit[2:] if nl else ()) + digit * (5 * int(nl)) + last
+    return CostPlan(w[0], w[1], w[2], w[3], tuple(w[4:4 + w[3]]), w[8], w[9], w[10], w[11], w[12], w[14], w[15], kernels)
+
+
+def cost_masks(extents, ops):
+    """The flat-index mask of the Z axes per row of ``ops`` (``(m, rank)`` codes 0 = I and 3 = Z over a tensor of shape
+    ``extents``, every extent 1 or 2), as an int64 array -- host only: what ``ctg_exec_result_cost`` forms.
+    ``ValueError`` for another code, Z on an axis of extent 1 and an extent above 2."""
+    ext = [int(v) for v in extents]
+    if any(v < 1 or v > 2 for v in ext):
+        raise ValueError(f"cost: the extents {tuple(ext)}; with terms every extent must be 1 or 2.")
+    raw = np.asarray(ops)
+    if raw.size and raw.dtype.kind not in "iub":
+        raise ValueError(f"cost: codes of dtype {raw.dtype}; integers 0 (I) and 3 (Z) are expected.")
+    arr = np.ascontiguousarray(raw, dtype=np.int64).reshape(-1, len(ext)) if len(ext) else np.zeros((int(raw.shape[0]) if raw.ndim else 0, 0), np.int64)
+    if arr.size and not np.all((arr == 0) | (arr == 3)):
+        raise ValueError("cost: a code is neither 0 (I) nor 3 (Z); X and Y terms are not a classical cost.")
+    stride = np.ones(len(ext), dtype=np.int64)
+    for a in range(len(ext) - 2, -1, -1):
+        stride[a] = stride[a + 1] * ext[a + 1]
+    for a, v in enumerate(ext):
+        if v != 2 and arr[:, a].any():
+            raise ValueError(f"cost: Z on axis {a} of extent {v}; only an axis of extent 2 carries Z.")
+    return ((arr == 3).astype(np.int64) * stride[None, :]).sum(axis=1)
 
 
 def pauli_apply_coeffs(coeffs, m):
@@ -1068,6 +1135,63 @@ class Executor:
     def pauli_spectrum_plan(self, extents, flips):
         """What ``pauli_spectrum(extents, flips)`` launches on this executor (:func:`pauli_spectrum_plan`)."""
         return pauli_spectrum_plan(self.plan.dtype, extents, flips)
+
+    # -- the distribution of a classical cost under p (csrc/ctg_cost.hip) -- #
+
+    COST_MAX_TERMS = COST_MAX_TERMS
+    COST_MAX_LEVELS = COST_MAX_LEVELS
+    COST_MAX_EDGES = COST_MAX_EDGES
+
+    def cost_result(self, extents, ops=None, coeffs=None, dev_cost=None, tail=-1, levels=(), edges=None, dev_cost_out=None):
+        """The statistics of a classical cost ``C(z)`` under ``p = |x|^2`` of the result tensor
+        (``ctg_exec_result_cost``): ``extents`` is the shape of the result.  The cost is either ``ops`` (``(m, rank)``
+        codes 0 = I, 3 = Z, every extent 1 or 2) with ``m`` real ``coeffs``, ``C(z) = sum_s coeffs[s] (-1)^popcount(z &
+        m_s)``, or ``dev_cost``, the device address of ``n`` doubles.  ``tail`` -1 (lower) or +1 (upper); up to
+        ``COST_MAX_LEVELS`` ``levels`` in (0, 1]; ``edges`` none or 2 .. ``COST_MAX_EDGES`` ascending finite numbers;
+        ``dev_cost_out`` a device address of ``n`` doubles that receives ``C``.  Returns ``(words, hist)``: the int64
+        array of ``COST_WORDS`` words laid out as include/ctg_hip.h documents (``words.view(np.float64)`` for the double
+        words) and the int64 array of ``len(edges) + 1`` integer masses (``None`` without edges).  ``ValueError`` for
+        what the call refuses (nothing is launched) and for a result whose ``sum p`` is not finite."""
+        ext = np.zeros(max(len(extents), 1), dtype=np.int64)
+        ext[:len(extents)] = [int(v) for v in extents]
+        rank = len(extents)
+        dp, u8p = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+        m, ops_p, co_p = 0, None, None
+        if ops is not None or coeffs is not None:
+            if ops is None or coeffs is None:
+                raise ValueError("cost: terms need both ops and coeffs.")
+            raw = np.asarray(ops)
+            if raw.size and (raw.dtype.kind not in "iub" or raw.min() < 0 or raw.max() > 255):
+                raise ValueError("cost: a code is no integer; 0 (I) or 3 (Z) per axis is expected.")
+            co = pauli_apply_coeffs(coeffs, len(raw) if raw.ndim else 0)
+            m = co.size
+            if raw.size != m * rank:
+                raise ValueError(f"cost: codes of shape {raw.shape}; ({m}, {rank}) is expected, one column per axis.")
+            arr = np.zeros(max(m * rank, 1), dtype=np.uint8)
+            arr[:m * rank] = raw.reshape(-1)
+            cobuf = np.zeros(max(m, 1), dtype=np.float64)
+            cobuf[:m] = co
+            ops_p, co_p = arr.ctypes.data_as(u8p), cobuf.ctypes.data_as(dp)
+        lev = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+        levbuf = np.zeros(max(lev.size, 1), dtype=np.float64)
+        levbuf[:lev.size] = lev
+        ed = None if edges is None else np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        ne = 0 if ed is None else ed.size
+        if ed is not None and ne == 0:
+            raise ValueError("cost: no edge is given; at least 2 are expected.")
+        hist = None if ed is None else np.zeros(ne + 1, dtype=np.int64)
+        words = np.zeros(COST_WORDS, dtype=np.int64)
+        if tail not in (-1, 1):
+            raise ValueError(f"cost: tail = {tail!r} is neither -1 (lower) nor +1 (upper).")
+        _check(load().ctg_exec_result_cost(
+            self.handle, rank, _i64p(ext), m, ops_p, co_p, C.c_void_p(int(dev_cost) if dev_cost else None), int(tail), lev.size,
+            levbuf.ctypes.data_as(dp), ne, None if ed is None else ed.ctypes.data_as(dp), _i64p(words),
+            None if hist is None else _i64p(hist), C.c_void_p(int(dev_cost_out) if dev_cost_out else None)))
+        return words, hist
+
+    def cost_plan(self, extents, source="terms", nl=0, ne=0):
+        """What ``cost_result`` launches on this executor (:func:`cost_plan`)."""
+        return cost_plan(self.plan.dtype, extents, source, nl, ne)
 
     # -- a Pauli sum applied to the result tensor (csrc/ctg_pauli_apply.hip) -- #
 

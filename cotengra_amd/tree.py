@@ -1119,6 +1119,16 @@ class ContractionTree:
 
         return _tree_contractor(self, order).pauli_spectrum(*arrays, flips=flips, paulis=paulis, **kwargs)
 
+    def contract_cost(self, arrays, terms=None, coeffs=None, values=None, order=None, **kwargs):
+        """:meth:`contract` followed by the statistics of a classical cost ``C(z)`` under the output distribution --
+        mean, variance, CVaR and quantiles, a histogram, the optimum and its probability -- on the device
+        (``HipContractor.cost``; ``kwargs``: ``levels``, ``edges``, ``tail``, ``keep_values``,
+        ``strip_exponent``, ``check_zero``, ``reuse``).  The cost: Z-type ``terms`` with real ``coeffs``, or an array of
+        ``values``.  Returns a ``CostResult``.  Not differentiable."""
+        from .contractor import _tree_contractor
+
+        return _tree_contractor(self, order).cost(*arrays, terms=terms, coeffs=coeffs, values=values, **kwargs)
+
     def contract_expectation(self, arrays, paulis, order=None, **kwargs):
         """:meth:`contract` followed by the expectation values ``<x| P |x>`` of the Pauli strings ``paulis`` over
         the output indices (a string over ``IXYZ``, a mapping ``{label: letter}``, a sequence of ``(label, letter)``

@@ -773,6 +773,71 @@ int ctg_rdm_wide_plan(int32_t dtype, int64_t rank, const int64_t* extents, const
 int ctg_exec_result_pauli_spectrum(ctg_exec* exec, int64_t rank, const int64_t* extents, const uint8_t* flips, int64_t m,
                                    const int64_t* select, double* out, void* dev_out);
 int ctg_pauli_spectrum_plan(int32_t dtype, int64_t rank, const int64_t* extents, const uint8_t* flips, int64_t* words);
+/* Added to ABI 10 WITHOUT a bump of CTG_ABI_VERSION likewise (two new symbols; a binding that needs them looks them up):
+ * the distribution of a classical cost C(z) under p(z) = |x_z|^2 over the result tensor x, on the device
+ * (csrc/ctg_cost.hip): conditional value at risk, quantiles, a histogram, moments, the optimum of C
+ * over all n bitstrings and the probability of sampling it.  extents[rank] is the shape of x, n elements.
+ * THE COST VECTOR C[0 .. n) (fp64) comes from exactly one of two sources.
+ *   - Terms: ops[m][rank] with codes 0 (I) and 3 (Z) only (the rows of ctg_exec_result_pauli), coeffs[m] finite, m <=
+ *     CTG_COST_MAX_TERMS; every extent must be 1 or 2 (n = 2^L).  C(z) = sum over s of coeffs[s] (-1)^popcount(z & m_s),
+ *     m_s the flat-index mask of the Z axes of row s (the flat bit of an axis is log2 of its row-major stride): bit 1 of z
+ *     means eigenvalue -1.  The host adds the coefficients of equal masks in ascending term order in fp64; the device
+ *     zeroes the vector, stores each unique (mask, coefficient) pair and runs, for the bits b = 0, 1, .., L - 1 IN THIS
+ *     ORDER, (a, c) = (v[j], v[j | 2^b]) -> (a + c, a - c), nothing contracted; every entry then gets + 0.0, so no -0.0
+ *     survives.  The bits of C are a function of (extents, ops, coeffs) alone.
+ *   - Values: dev_cost, n doubles on the device (8-byte aligned), any extents; never written.  A first pass refuses an
+ *     entry that is not finite (CTG_E_INVALID, all outputs untouched).  -0.0 counts as +0.0.
+ * INTEGER WEIGHTS.  S = sum p as ctg_exec_result_stats returns it = f 2^e, f in [1/2, 1); s = 62 - e (s = 0 for S = 0);
+ * w_i = (uint64) rint(p_i 2^s): the scaling is exact, there is one rounding.  W = sum w < 2^63.  Every mass below is a
+ * sum of w by 64-bit integer additions (order cannot matter; no floating-point atomics); divide by 2^s, and by S to
+ * normalise.  An all-zero tensor: s = 0, W = 0, every mass 0, every level's A = 0 and t = +0.0, the support's extremes
+ * 0.0 with index -1.  CTG_E_NORM when S is not finite.
+ * LEVELS.  levels[nl], nl <= CTG_COST_MAX_LEVELS, each in (0, 1]; tail = -1 (lower) or +1 (upper).  A_l = ceil(alpha_l W)
+ * exactly (alpha_l is a dyadic rational).  Lower tail: t_l = min{ c : sum over C(z) <= c of w_z >= A_l }, below_l = sum
+ * over C(z) < t_l of w_z, at_l = sum over C(z) = t_l of w_z, tail_l = sum over C(z) < t_l of p_z C(z) (fp64).  The upper
+ * tail is the same on -C, reported in C's own sign.  CVaR_l = (tail_l + (A_l - below_l) 2^-s t_l) / (A_l 2^-s).
+ * HISTOGRAM.  edges[ne], ne = 0 or 2 <= ne <= CTG_COST_MAX_EDGES, finite, strictly ascending.  out_hist[ne + 1]:
+ * out_hist[k] = sum of w_z over the z with k edges <= C(z), i.e. k = numpy's searchsorted(edges, C, "right"):
+ * out_hist[0] the mass below the first edge, out_hist[ne] the mass at or above the last, out_hist[1 .. ne - 1] the bins.
+ * out_words[CTG_COST_WORDS], each word an int64 (i) or the bits of a double (d):
+ *   [0] s (i)   [1] W (i)   [2] sum p C (d)   [3] sum (p C) C (d)   [4] min C (d)  [5] its lowest flat index (i)
+ *   [6] max C (d)  [7] its lowest index (i)   [8] min C over the support w > 0 (d)  [9] its lowest index (i)  [10] the
+ *   mass at that value (i)   [11] max C over the support (d)  [12] index (i)  [13] mass (i)   [14] nl (i)  [15] tail (i)
+ *   [16] S (d)   [17 .. 23] 0   [24 + 5 l ..]: A_l (i), t_l (d), below_l (i), at_l (i), tail_l (d)
+ * fp64 sums (p C is one rounded product of SampleElem's p, (p C) C another) have a fixed association that depends on n
+ * alone: a thread adds its 16 elements of a chunk of 4096 in index order, the wave by xor-butterflies, the four waves in
+ * order, the chunks of a workgroup's contiguous span ascending, the spans ascending.  |sum - exact| <= (n + 5) 2^-53 sum
+ * p |C|^k.
+ * dev_cost_out, optional: n doubles on the device, 8-byte aligned, overlapping neither the result nor dev_cost; receives
+ * C.  The call is synchronous; the tensor is read as the calls above read it and never written.  CTG_E_INVALID --
+ * checked on the host before anything is reserved or launched, all outputs untouched -- for a null exec, extents or
+ * out_words, what ctg_exec_result_pauli refuses about rank and extents, both sources or neither, ops without coeffs or
+ * the reverse, a code other than 0 and 3, Z on an axis of extent 1, an extent above 2 with terms, m, nl or ne out of
+ * range, a level outside (0, 1], edges not finite or not ascending, edges without out_hist, a coefficient that is not
+ * finite (or whose absolute sum is not), a tail other than -1 and +1, a misaligned or overlapping dev_cost / dev_cost_out.
+ * ctg_cost_plan (host only, touches no device) returns what the call launches for a result of `dtype` whose extents'
+ * product stands for result_elems, source CTG_COST_TERMS or CTG_COST_VALUES, the same refusals included:
+ *   words[0] L (values: -1)   [1] n   [2] tile bits min(L, 12) of "cost_tile_kernel"   [3] launches of "cost_pass_kernel"
+ *   [4 .. 7] their bits   [8] workgroups of a transform launch   [9] digit passes per level: 6 (12, 12, 12, 12, 12, 4
+ *   bits; without levels 1, which gives W)   [10] launches of "cost_digit_kernel<T>": 1 + 5 nl, each followed by
+ *   "cost_rowsum_kernel" and "cost_select_kernel"   [11] workgroups of a digit pass and of "cost_final_kernel<T,H>"
+ *   [12] scratch bytes with the vector in the scratch and no term table (16 bytes per unique mask more; 8 n less when
+ *   dev_cost or dev_cost_out holds C)   [13] the dtype code   [14] chunks of 4096 elements   [15] histogram words ne + 1
+ * Scratch: the buffer of ctg_exec_result_topk (counted by ctg_exec_device_bytes, freed by ctg_exec_destroy).  Not
+ * differentiable; no multi-rank entry, as above. */
+#define CTG_COST_MAX_TERMS (1 << 20)
+#define CTG_COST_MAX_LEVELS 8
+#define CTG_COST_MAX_EDGES 4097
+#define CTG_COST_WORDS 64
+#define CTG_COST_LEVEL_WORD0 24
+#define CTG_COST_LEVEL_WORDS 5
+#define CTG_COST_PLAN_WORDS 16
+#define CTG_COST_TERMS 0
+#define CTG_COST_VALUES 1
+int ctg_exec_result_cost(ctg_exec* exec, int64_t rank, const int64_t* extents, int64_t m, const uint8_t* ops, const double* coeffs,
+                         const void* dev_cost, int32_t tail, int64_t nl, const double* levels, int64_t ne, const double* edges,
+                         int64_t* out_words, int64_t* out_hist, void* dev_cost_out);
+int ctg_cost_plan(int32_t dtype, int64_t rank, const int64_t* extents, int32_t source, int64_t nl, int64_t ne, int64_t* words);
 /* debugging aid: copy `n` elements of the arena starting at element `offset`
  * to the host (synchronous) */
 int ctg_exec_download_arena(ctg_exec* exec, int64_t offset, int64_t n, void* host_out);

@@ -14,7 +14,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCES = ["ctg_sample.hip", "ctg_reduce.hip", "ctg_rdm.hip", "ctg_rdm_wide.hip", "ctg_pauli.hip", "ctg_pauli_apply.hip", "ctg_op_apply.hip",
-           "ctg_pauli_spectrum.hip"]
+           "ctg_pauli_spectrum.hip", "ctg_cost.hip"]
 FIELDS = [("VGPRs", "vgpr"), ("AGPRs", "agpr"), ("TotalSGPRs", "sgpr"), ("ScratchSize [bytes/lane]", "scratch"),
           ("LDS Size [bytes/block]", "lds"), ("Occupancy [waves/SIMD]", "occ")]
 
